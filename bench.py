@@ -21,9 +21,15 @@ secondary key `bf16x3_mode` — never as `value`.
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.  `--backend gloo --dry-net` runs the same launch /
 barrier / gather / paste code with a stand-in network on CPU (tests/test_bench_launch.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel by summed time,
-HIP-event timed on the launch stream) and `cpu_baseline` (stock-torch CPU restatement and the C oracle timed on a
-bounded sample on this box's host cores; N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times `--steps` steps and
+prints the headline figure (`value`, `ms_per_step`).  `--full` adds everything else after the timed region: MFMA clock probes,
+package power, `roofline` (dominant kernel by summed time, HIP-event timed on the launch stream; HBM traffic from rocprofv3
+--pmc passes), the secondary decoder / linear-math legs, `other_configs`, `cpu_baseline` + `vq_index_match` (stock-torch CPU
+restatement and the C oracle timed on a bounded sample on the host cores; N=1 only) and, on N > 1, the strong-scaling leg.
+
+`--dump-outputs DIR` writes what the last timed step computed (the arrays a caller of the timed path receives) as
+DIR/<name>.npy, float32 (float64 for integer arrays), at most DUMP_MAX_BYTES in all; a larger output is written as a fixed
+seeded sample of its flat positions.  Weights and inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -285,6 +291,37 @@ def physical_cores():
     return os.cpu_count() or 1
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6        # --dump-outputs: all .npy files together (headers included)
+DUMP_SEED = 0
+
+
+def dump_outputs(d, arrays):
+    """Write {name: tensor} as d/<name>.npy: floating arrays as float32, integer arrays as float64 (exact).  When the arrays do not
+    fit DUMP_MAX_BYTES together, each is cut to its share of the budget: the values at the sorted, de-duplicated flat positions
+    np.random.default_rng(DUMP_SEED).integers(0, numel, share) - the same positions in every run of the same arguments.
+    Returns {name: {'shape', 'dtype', 'written'}} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    header = 128                                    # bytes of a .npy header (version 1.0, short shapes)
+    isz = {n: 4 if t.is_floating_point() else 8 for n, t in arrays.items()}
+    need = sum(t.numel() * isz[n] + header for n, t in arrays.items())
+    scale = min(1.0, (DUMP_MAX_BYTES - header * len(arrays)) / max(1, need - header * len(arrays)))
+    info = {}
+    for n, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        if scale < 1.0:
+            k = int(t.numel() * scale)
+            pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), k, dtype=np.int64))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        a = flat.to(torch.float32 if isz[n] == 4 else torch.float64).cpu().numpy()
+        np.save(os.path.join(d, f'{n}.npy'), a if scale < 1.0 else a.reshape(tuple(t.shape)))
+        info[n] = {'shape': list(t.shape), 'dtype': str(a.dtype),
+                   'written': 'all' if scale >= 1.0 else f'{a.size} values at seeded flat positions (seed {DUMP_SEED})'}
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -320,7 +357,14 @@ def main():
     ap.add_argument('--no-measure-traffic', action='store_true',
                     help='do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; ~20 s each) that make roofline.traffic a number of THIS run; '
                          'the line then carries the figure of profiles/pmc_traffic.json, stamped as such')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure and check everything beyond the headline figure (clock probes, power, roofline '
+                         'and traffic, secondary legs, other configs, CPU baseline and VQ index match, strong-scaling leg on N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -394,8 +438,8 @@ def main():
         x = torch.from_numpy(synth.synth_input(1000 + rank, (B, 3, wl['hw'], wl['hw']))).to(dev)
         do_gather = False
 
-        def step():
-            return net.test(x) if wl['fn'] == 'test' else net(x)[0]
+        def step():      # (forward: the whole tuple a caller receives - image, two losses, index maps)
+            return net.test(x) if wl['fn'] == 'test' else net(x)
         out_mpix = world * B * wl['out_hw'] * wl['out_hw'] / 1e6
         scaling = 'weak'
         workload = wl['text'].format(B=B) + ' per GPU, synthetic random weights (seed 0; codebook drawn at the scale of z), inputs resident in HBM'
@@ -440,12 +484,12 @@ def main():
         sync()
         return round(float(ticks.double().mean().item()) / (e0.elapsed_time(e1) * 1e-3) / 1e9, 3)
 
-    clk_before = clock_probe()       # ahead of the warm-up: the timed steps follow the warm-up steps directly (with the probe between them the
-    for _ in range(args.warmup):     # first timed step ran 4 ms slow - the chip leaves the probe's pure-MFMA loop in another power state)
+    clk_before = clock_probe() if args.full else None     # ahead of the warm-up: the timed steps follow the warm-up steps directly (with the probe
+    for _ in range(args.warmup):     # between them the first timed step ran 4 ms slow - the chip leaves the probe's pure-MFMA loop in another power state)
         step()
     fence()
     watch = None
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         pr = torch.cuda.get_device_properties(dev)
         watch = PowerWatch((pr.pci_domain_id, pr.pci_bus_id, pr.pci_device_id) if hasattr(pr, 'pci_bus_id') else None)
         if watch.dir:                      # file reads on a host thread: safe inside the timed region (rocm-smi is sampled in its own loop below)
@@ -461,8 +505,17 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     dt_rank = dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if isinstance(y, tuple):          # forward: (image, codebook loss, semantic loss, [index map per codebook])
+            outs = {'output': y[0], 'codebook_loss': y[1], 'semantic_loss': y[2], **{f'indices_{i}': t for i, t in enumerate(y[3])}}
+        else:                             # tiles16 with the all-gather: every rank's tiles of the last step, as the paste receives them
+            outs = {'output': sg.result(nstep[0] - 1) if (args.workload == 'tiles16' and sg is not None) else y}
+        dumped = dump_outputs(args.dump_outputs, outs)
+    if isinstance(y, tuple):
+        y = y[0]
     power = watch.stop() if (watch and watch.dir) else None
-    clk_after = clock_probe()
+    clk_after = clock_probe() if args.full else None
     per_rank_ms = [round(dt / args.steps * 1e3, 3)]
     if world > 1:
         tall = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
@@ -530,13 +583,15 @@ def main():
         res['timed_region']['last_step_split_ms_per_rank'] = split
     if args.workload == 'tiles16' and do_gather:
         res['config']['gather_overlap'] = 'all-gather of step k overlaps step k+1'
+    if dumped:
+        res['dump_outputs'] = dumped
 
     # ---------------------------------------------------------------- strong-scaling leg (all ranks; after the timed region of record)
-    # the driver runs ONE command per N.  With N > 1 the default (weak-scaling) workload therefore appends BASELINE
+    # ONE command per N.  With N > 1 and --full the default (weak-scaling) workload therefore appends BASELINE
     # config 3a - one 2048x2048 LR image = 256 tiles of 128x128, sharded over the ranks by the work-balanced partition, ONE RCCL all-gather
     # of the upscaled tiles, paste on rank 0 - so that the same JSON line records a point of the strong curve too, with each rank's
     # compute / gather / paste split.  (`--workload tile2048` is the same thing as the workload of record, with every rank pasting.)
-    if world > 1 and args.workload == 'tiles16' and not args.no_strong_leg and use_pg:
+    if args.full and world > 1 and args.workload == 'tiles16' and not args.no_strong_leg and use_pg:
         if sg is not None:
             sg.wait_all()
         S = 512 if dry else args.image
@@ -581,7 +636,7 @@ def main():
         del img, ys
 
     # ---------------------------------------------------------------- rank-0 extras (not part of the timed region)
-    if rank == 0 and not dry:
+    if rank == 0 and not dry and args.full:
         x16 = x if (args.workload == 'tiles16' or wl) else torch.from_numpy(synth.synth_input(1000, (B, 3, 128, 128))).to(dev)
         run16 = (lambda t: net(t)[0]) if (wl and wl['fn'] == 'forward') else net.test          # the unit forward of this workload
         # Per-kernel roofline: HIP events around every launch on the launch stream.  With >1 sub-batch streams kernels
@@ -750,7 +805,7 @@ def main():
             net.decoder_math = args.decoder_math
             net.linear_math = args.linear_math
         if world == 1 and not args.no_second_leg and args.workload == 'tiles16' and not args.no_other_configs:
-            # BASELINE configs 4 and 5 as short legs of the DEFAULT run (VERDICT r5 "missing" 3: the driver runs this command only, so the
+            # BASELINE configs 4 and 5 as short legs of the default workload's --full run (VERDICT r5 "missing" 3: the driver runs this command only, so the
             # x2 / HQ numbers were the builder's alone): the same step functions as `--workload x2b32 | hq8`, a few steps each, the product
             # default modes, inputs resident in HBM.  Secondary information - `value` above is config 2.
             others = {}
