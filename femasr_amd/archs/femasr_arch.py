@@ -282,8 +282,8 @@ class FeMaSRNet(nn.Module):
             _lib.check(lib.femasr_set_linear_math(self._handle, {'fp32': 0, 'bf16_split': 1}[self.linear_math]))
             _lib.check(lib.femasr_set_streams(self._handle, int(self.num_streams)))
             _lib.check(lib.femasr_set_decoder_math(self._handle, {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3}[self.decoder_math]))
-            if self.debug_wino_limits is not None:
-                _lib.check(lib.femasr_debug_set_wino_limits(self._handle, int(self.debug_wino_limits[0]), int(self.debug_wino_limits[1])))
+            lim = (0, 0) if self.debug_wino_limits is None else self.debug_wino_limits      # (0, 0): the handle's defaults again
+            _lib.check(lib.femasr_debug_set_wino_limits(self._handle, int(lim[0]), int(lim[1])))
             self._streams_set = (self._handle.value, self.num_streams, self.decoder_math, self.linear_math, self.debug_wino_limits)
         return lib, self._handle
 

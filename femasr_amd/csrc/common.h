@@ -53,7 +53,7 @@ int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out);
 
 // 1x1 convs / nn.Linear as an fp32-grade product on the bf16 matrix pipe (kernels_gemm_bf16.hip)
 bool femasr_gemm_bf16s_shape_ok(const femasr_conv_args *a);
-bool femasr_conv3x3_bf16s_shape_ok(const femasr_conv_args *a);      // the 3x3 stride-1 pad-1 form (K = 9 Cin) of the same kernel
+bool femasr_conv3x3_bf16s_shape_ok(const femasr_conv_args *a);      // the 3x3 pad-1 form (K = 9 Cin, stride 1 or 2) of the same kernel
 int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const void *w_bf16s, int *variant_out, double *flops_out);
 int femasr_gemm_bf16s_variant_count();
 const char *femasr_gemm_bf16s_variant_name(int v);
@@ -78,3 +78,18 @@ bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a);      // the same ru
 int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
 int femasr_conv_bf16x3_variant_count();
 const char *femasr_conv_bf16x3_variant_name(int v);
+
+// The forms a conv runs in, in profile-slot order (femasr_create lays the slots out from this list)
+enum ConvForm {
+    CONV_DIRECT,      // fp32 halo / implicit-GEMM kernels, the VALU out_conv kernel (kernels_conv.hip, kernels_gemm.hip)
+    CONV_BF16X3,      // bf16x3 halo kernels (w_bf16x3)
+    CONV_WINO,        // Winograd F(4x4,3x3) (w_wino)
+    CONV_WINO_UP2,    // the 25-product form of nearest-x2 + 3x3 conv (w_wino with up2)
+    CONV_SPLIT,       // split-bf16 GEMM: 1x1 / linear layer, or 3x3 conv over K = 9 Cin (w_bf16s)
+    CONV_FORM_COUNT
+};
+int femasr_conv_form_variant_count(ConvForm f);
+const char *femasr_conv_form_variant_name(ConvForm f, int v);
+// Launches the conv in form f (the form's weight image in its femasr_conv_args field; w_bf16s for CONV_SPLIT).  *slot_out: the
+// launch's profile slot counted from the first conv slot (variants of the forms before f, then the variant that ran).
+int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a, int *slot_out, double *flops_out);

@@ -476,7 +476,7 @@ extern "C" int femasr_debug_mfma_bf16(void *stream, const uint16_t *a, const uin
 
 int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const void *w_bf16s, int *variant_out, double *flops_out)
 {
-    FEMASR_REQUIRE(a && a->in && w_bf16s && femasr_gemm_bf16s_shape_ok(a), "gemm_bf16s: layer is neither a 1x1 / linear layer nor a 3x3 stride-1 pad-1 conv with Cin %% 64 == 0");
+    FEMASR_REQUIRE(a && a->in && w_bf16s && femasr_gemm_bf16s_shape_ok(a), "gemm_bf16s: layer is neither a 1x1 / linear layer nor a 3x3 pad-1 conv of stride 1 or 2 with Cin %% 64 == 0");
     FEMASR_REQUIRE(a->bias && a->out, "gemm_bf16s: bias/out must be set");
     FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm_bf16s: bad activation %d", a->act);
     const bool conv = a->ksz == 3;

@@ -1168,27 +1168,53 @@ int femasr_clock_probe(void *stream, int mfmas_per_wave, unsigned long long *tic
     return FEMASR_OK;
 }
 
-int femasr_conv2d(void *stream, const femasr_conv_args *a)
+}  // extern "C"
+
+// ---- conv launch by form (femasr_conv2d and the model's schedule; profile slots in ConvForm order)
+int femasr_conv_form_variant_count(ConvForm f)
+{
+    const int n[CONV_FORM_COUNT] = {femasr_conv_variant_count(), femasr_conv_bf16x3_variant_count(), femasr_conv_wino_variant_count(), 1,
+                                    femasr_gemm_bf16s_variant_count()};
+    return n[f];
+}
+
+const char *femasr_conv_form_variant_name(ConvForm f, int v)
+{
+    switch (f) {
+    case CONV_BF16X3: return femasr_conv_bf16x3_variant_name(v);
+    case CONV_WINO: return femasr_conv_wino_variant_name(v);
+    case CONV_WINO_UP2: return femasr_conv_wino_up2_variant_name();
+    case CONV_SPLIT: return femasr_gemm_bf16s_variant_name(v);
+    default: return femasr_conv_variant_name(v);
+    }
+}
+
+int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a, int *slot_out, double *flops_out)
+{
+    int v = 0, r;
+    switch (f) {
+    case CONV_BF16X3: r = femasr_conv_bf16x3_launch(s, a, &v, flops_out); break;
+    case CONV_WINO: r = femasr_conv_wino_launch(s, a, &v, flops_out); break;
+    case CONV_WINO_UP2: r = femasr_conv_wino_up2_launch(s, a, flops_out); break;
+    case CONV_SPLIT: r = femasr_gemm_bf16s_launch(s, a, a->w_bf16s, &v, flops_out); break;
+    default: r = femasr_conv2d_launch(s, a, nullptr, &v, flops_out); break;
+    }
+    for (int g = 0; g < f; ++g) v += femasr_conv_form_variant_count((ConvForm)g);
+    if (slot_out) *slot_out = v;
+    return r;
+}
+
+extern "C" int femasr_conv2d(void *stream, const femasr_conv_args *a)
 {
     FEMASR_REQUIRE(!a || !a->in_add || (a->w_wino && a->up2 && !a->w_bf16x3 && !a->w_bf16s),
                    "conv2d: in_add is only taken by the x2 Winograd-type form (up2 = 1 with w_wino, no w_bf16x3 / w_bf16s)");
-    if (a && a->w_bf16s) {
-        FEMASR_REQUIRE(femasr_gemm_bf16s_shape_ok(a), "conv2d: w_bf16s given but the layer is not a 1x1 stride-1 layer with Cin %% 64 == 0 and no prologue");
-        return femasr_gemm_bf16s_launch((hipStream_t)stream, a, a->w_bf16s, nullptr, nullptr);
-    }
-    if (a && a->w_bf16x3) {
-        FEMASR_REQUIRE(femasr_conv_bf16x3_eligible(a), "conv2d: w_bf16x3 given but the layer is not eligible for the bf16x3 path");
-        return femasr_conv_bf16x3_launch((hipStream_t)stream, a, nullptr, nullptr);
-    }
-    if (a && a->w_wino && a->up2) {
-        FEMASR_REQUIRE(femasr_conv_wino_up2_shape_ok(a), "conv2d: w_wino given with up2 but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0, no prologue");
-        return femasr_conv_wino_up2_launch((hipStream_t)stream, a, nullptr);
-    }
-    if (a && a->w_wino) {
-        FEMASR_REQUIRE(femasr_conv_wino_shape_ok(a), "conv2d: w_wino given but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0");
-        return femasr_conv_wino_launch((hipStream_t)stream, a, nullptr, nullptr);
-    }
-    return femasr_conv2d_launch((hipStream_t)stream, a, nullptr, nullptr, nullptr);
+    // the form whose weights are given
+    const ConvForm f = !a ? CONV_DIRECT : a->w_bf16s ? CONV_SPLIT : a->w_bf16x3 ? CONV_BF16X3 : !a->w_wino ? CONV_DIRECT : a->up2 ? CONV_WINO_UP2 : CONV_WINO;
+    FEMASR_REQUIRE(f != CONV_SPLIT || femasr_gemm_bf16s_shape_ok(a),
+                   "conv2d: w_bf16s given but the layer is neither a 1x1 stride-1 layer nor a 3x3 pad-1 conv of stride 1 or 2, with Cin %% 64 == 0 and no prologue");
+    FEMASR_REQUIRE(f != CONV_BF16X3 || femasr_conv_bf16x3_eligible(a), "conv2d: w_bf16x3 given but the layer is not eligible for the bf16x3 path");
+    FEMASR_REQUIRE(f != CONV_WINO_UP2 || femasr_conv_wino_up2_shape_ok(a),
+                   "conv2d: w_wino given with up2 but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0, no prologue");
+    FEMASR_REQUIRE(f != CONV_WINO || femasr_conv_wino_shape_ok(a), "conv2d: w_wino given but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0");
+    return femasr_conv_form_launch((hipStream_t)stream, f, a, nullptr, nullptr);
 }
-
-}  // extern "C"

@@ -78,11 +78,12 @@ struct WSpec {
     WKind kind;
     int64_t shape[4];
     int ndim;
-    float *dev = nullptr;   // repacked, owned
-    void *split = nullptr;  // bf16x3 hi/lo fragments (decoder-side 3x3 convs only), owned
-    void *lin3 = nullptr;   // three bf16 planes of a 1x1 / linear weight (femasr_repack_k1_bf16s), owned
-    float *up2w = nullptr;  // phase matrices of a nearest-x2 conv (femasr_repack_oihw_up2), owned
-    float *wino = nullptr;  // Winograd-domain weights (decoder-side 3x3 convs of single-codebook networks), owned
+    // owned weight images; femasr_set_weight builds those of every form the layer can take (layer_forms)
+    float *dev = nullptr;   // repacked fp32 (CONV_DIRECT)
+    float *up2w = nullptr;  // phase matrices of a nearest-x2 conv (femasr_repack_oihw_up2; CONV_DIRECT on the halo kernels)
+    void *bf16x3 = nullptr; // bf16x3 hi/lo fragments (CONV_BF16X3)
+    float *wino = nullptr;  // Winograd-domain weights (CONV_WINO / CONV_WINO_UP2)
+    void *bf16s = nullptr;  // three bf16 planes of the (K x Cout) matrix (CONV_SPLIT: femasr_repack_k1_bf16s / femasr_repack_oihw_bf16s)
     bool up2 = false;       // the conv behind nn.Upsample(x2) of an up / decoder block
     bool set = false;
     size_t numel() const { size_t n = 1; for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i]; return n; }
@@ -110,7 +111,7 @@ bool behind_every_lookup(const femasr_config &cfg, int encode_depth, int last_qu
 struct T {          // NHWC activation view
     float *p = nullptr;
     int B = 0, H = 0, W = 0, C = 0;
-    double *gn_part = nullptr;   // fused GroupNorm partial moments written by the producing bf16x3 conv (or null)
+    double *gn_part = nullptr;   // fused GroupNorm partial moments written by the producing conv's epilogue (or null; gn_tiles)
     int gn_tiles = 0;
     size_t numel() const { return (size_t)B * H * W * C; }
 };
@@ -164,6 +165,12 @@ struct Arena {
 
 struct ProfRec { int slot; hipEvent_t e0, e1; double flops, bytes; };
 
+struct ConvModes {          // the handle's settings that choose the form of a conv (conv_form)
+    int decoder_math = 0;   // femasr_set_decoder_math
+    int linear_math = 1;    // femasr_set_linear_math: 1 = fp32-grade product on the bf16 matrix pipe, 0 = fp32 MFMA chain
+    int wino_log2_total = FEMASR_WINO_LOG2_TOTAL, wino_log2_image = FEMASR_WINO_LOG2_IMAGE;      // femasr_debug_set_wino_limits (planner only)
+};
+
 }  // namespace
 
 struct femasr_handle {
@@ -183,11 +190,9 @@ struct femasr_handle {
     std::vector<double> acc_ms, acc_flops, acc_bytes;
     std::vector<int64_t> acc_n;
     std::vector<std::string> slot_names;
+    ConvModes modes;
     // sub-batch streams (femasr_set_streams): independent samples run on separate streams so that
     // one sub-batch's kernels fill the tail / HBM-bound phases of the other's
-    int decoder_math = 0;   // femasr_set_decoder_math
-    int linear_math = 1;    // femasr_set_linear_math: 1 = fp32-grade product on the bf16 matrix pipe, 0 = fp32 MFMA chain
-    int wino_log2_total = FEMASR_WINO_LOG2_TOTAL, wino_log2_image = FEMASR_WINO_LOG2_IMAGE;      // femasr_debug_set_wino_limits (planner only)
     int nsub = 1;
     std::vector<hipStream_t> sub_streams;
     std::vector<hipEvent_t> sub_done;
@@ -337,6 +342,65 @@ int build_specs(femasr_handle *h)
     return FEMASR_OK;
 }
 
+// ---------------------------------------------------------------- conv forms
+// The form a conv runs in, decided here and nowhere else: from the modes, the layer's key and the shape-only conv arguments, never
+// from a pointer, so the dry run that sizes the workspace and the real run pick the same form, the decoder schedules its skip adds by
+// it (run_tail) and femasr_set_weight packs the weights of every form it can pick (layer_forms).  Precedence: bf16x3, Winograd, split
+// 3x3, split 1x1, direct.  The size limits inside the eligibility helpers only ever send a layer to the direct form.
+ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string &key, const femasr_conv_args &a)
+{
+    const bool behind = behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, key);
+    if (behind && m.decoder_math == 1 && a.Cout > 4 && femasr_conv_bf16x3_shape_ok(&a)) return CONV_BF16X3;   // out_conv: exact VALU kernel in every mode
+    // exact-fp32 mode: convs behind every codebook lookup run in the Winograd F(4x4,3x3) form, the x2 convs in the 25-product form
+    // (they cannot move a VQ index; oracle: OracleNet.wino).  decoder_math 2 = 'fp32_direct' keeps the direct form; 0 runs the
+    // SiLU of their GroupNorm prologue on the hardware exp2 / rcp units, 3 = 'fp32_strict' keeps it IEEE-exact (== oracle).
+    if (behind && (m.decoder_math == 0 || m.decoder_math == 3)) {
+        if (femasr_conv_wino_up2_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO_UP2;
+        if (femasr_conv_wino_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO;
+    }
+    if (m.linear_math == 1) {
+        // a 3x3 conv in FRONT of a lookup (encoder down convs and ResBlocks, the conv behind every RSTB) runs as the split-bf16 GEMM
+        // over K = 9 Cin - the arithmetic of the linear layers (oracle: conv3x3_bf16s).  Its GroupNorm + SiLU prologue becomes a pass
+        // of its own (the GEMM takes plain rows).
+        femasr_conv_args plain = a;
+        plain.prologue = FEMASR_PRO_NONE;
+        if (!behind && (a.prologue == FEMASR_PRO_NONE || a.prologue == FEMASR_PRO_GN_SILU) && femasr_conv3x3_bf16s_shape_ok(&plain)) return CONV_SPLIT;
+        if (a.ksz == 1 && femasr_gemm_bf16s_shape_ok(&a)) return CONV_SPLIT;
+    }
+    return CONV_DIRECT;
+}
+
+// Fused GroupNorm partial moments a conv of this form writes when its output feeds a GroupNorm: tiles per sample, 0 = none (the
+// GroupNorm then runs the stand-alone moments kernel, which gives the same coefficients bit for bit).
+int gn_tiles(ConvForm f, const femasr_conv_args &a)
+{
+    const bool fusable = femasr_gn_fusable(a.Cout);
+    switch (f) {
+    case CONV_SPLIT: return 0;
+    case CONV_BF16X3: return fusable && a.Cout <= 256 ? ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16) : 0;       // <= 8 channels per group
+    case CONV_WINO:
+    case CONV_WINO_UP2: return femasr_conv_halo_eligible(&a) && fusable ? femasr_conv_wino_gn_tiles(a.Ho, a.Wo) : 0;      // per 16x16-pixel sub-block
+    default:       // halo kernels: per 8x16 tile; an x2 conv (phase filters) per half-resolution tile and phase
+        if (!femasr_conv_halo_eligible(&a) || !fusable) return 0;
+        return a.up2 ? 4 * ((a.H + 7) / 8) * ((a.W + 15) / 16) : ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
+    }
+}
+
+// The forms a conv / linear layer can take under any mode.  conv_form on the layer at a small size, stride 1, no prologue, no
+// activation and the default Winograd limits: every eligibility helper that accepts some call of the layer accepts this one (stride 2,
+// a prologue, an activation or a size limit only ever narrow the choice, and the last falls back to the direct form).
+std::array<bool, CONV_FORM_COUNT> layer_forms(const femasr_handle *h, const WSpec &w)
+{
+    femasr_conv_args a{};
+    a.B = 1; a.H = 16; a.W = 16; a.Cin = (int)w.shape[1]; a.Cout = (int)w.shape[0];
+    a.ksz = w.kind == W_CONV ? (int)w.shape[2] : 1; a.stride = 1; a.pad = a.ksz / 2; a.up2 = w.up2;
+    std::array<bool, CONV_FORM_COUNT> can{};
+    ConvModes m;
+    for (m.decoder_math = 0; m.decoder_math <= 3; ++m.decoder_math)
+        for (m.linear_math = 0; m.linear_math <= 1; ++m.linear_math) can[conv_form(h, m, w.key, a)] = true;
+    return can;
+}
+
 // ---------------------------------------------------------------- forward-time helpers
 struct Ctx {
     femasr_handle *h;
@@ -348,12 +412,13 @@ struct Ctx {
     bool dry() const { return arena->dry; }
     hipStream_t s() const { return stream; }
 
-    const float *Wt(const std::string &key)
+    const WSpec *spec(const std::string &key)
     {
         auto it = h->index.find(key);
         if (it == h->index.end()) { if (!rc) rc = femasr_set_error(FEMASR_ERR_WEIGHT, "internal: unknown weight %s", key.c_str()); return nullptr; }
-        return h->specs[it->second].dev;
+        return &h->specs[it->second];
     }
+    const float *Wt(const std::string &key) { const WSpec *w = spec(key); return w ? w->dev : nullptr; }
     float *alloc_f(size_t n)
     {
         void *p = arena->alloc(n * sizeof(float));
@@ -374,70 +439,56 @@ struct Ctx {
         int pro = FEMASR_PRO_NONE;
         const float *pa = nullptr, *pb = nullptr, *pc = nullptr;
         const float *res1 = nullptr, *res2 = nullptr;
-        const float *in_add = nullptr;   // second input, added while staging: only when up2_wino_ok() said the x2 Winograd-type form will run
-        bool lowp = false;       // behind the VQ lookup: may use the bf16x3 path when the handle opts in
-        bool want_gn = false;    // the output feeds a GroupNorm: let a bf16x3 conv emit its partial moments
+        const float *in_add = nullptr;   // second input, added while staging: only for a conv in the x2 Winograd-type form (run_tail)
+        bool want_gn = false;    // the output feeds a GroupNorm: let the conv emit its partial moments where its form can
     };
-    T conv(const T &x, const std::string &prefix, int cout, const ConvOpt &o)
+    // the arguments of a conv on x, without weights, output and GroupNorm partials (pointers may be null in the dry run)
+    femasr_conv_args conv_args(const T &x, int cout, const ConvOpt &o) const
     {
         const int Hv = o.up2 ? 2 * x.H : x.H, Wv = o.up2 ? 2 * x.W : x.W;
-        const int Ho = (Hv + 2 * o.pad - o.ksz) / o.stride + 1, Wo = (Wv + 2 * o.pad - o.ksz) / o.stride + 1;
-        T y = alloc_t(x.B, Ho, Wo, cout);
-        // The args struct is populated (shapes; pointers may be null in the dry run) BEFORE the planning decisions, and the
-        // same eligibility helpers decide in the dry and in the real run, so both plan identical buffers.
         femasr_conv_args a{};
         a.in = x.p; a.B = x.B; a.H = x.H; a.W = x.W; a.Cin = x.C;
         a.Cout = cout; a.ksz = o.ksz; a.stride = o.stride; a.pad = o.pad; a.up2 = o.up2;
         a.prologue = o.pro; a.pro_a = o.pa; a.pro_b = o.pb; a.pro_c = o.pc;
-        a.act = o.act; a.res1 = o.res1; a.res2 = o.res2; a.out = y.p; a.Ho = Ho; a.Wo = Wo;
-        a.in_add = o.in_add;
-        const void *split = nullptr;
-        // (several codebooks: the decoder feeds the later lookups through before_quant_group[q > 0]: only the convs that follow the LAST
-        // lookup may take the bf16x3 / Winograd forms - behind_every_lookup)
-        const bool behind = o.lowp && behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, prefix);
-        if (behind && h->decoder_math == 1) {
-            auto it = h->index.find(prefix + ".weight");
-            if (it != h->index.end()) split = h->specs[it->second].split;
-        }
-        const bool lowp_on = split != nullptr && cout > 4 && femasr_conv_bf16x3_shape_ok(&a);      // out_conv: exact VALU kernel in both modes
-        // exact-fp32 mode: convs behind every codebook lookup run in the Winograd F(4x4,3x3) form
-        // (they cannot move a VQ index; oracle: OracleNet.wino).  decoder_math 2 = 'fp32_direct' keeps the direct form; 0 runs the
-        // SiLU of their GroupNorm prologue on the hardware exp2 / rcp units, 3 = 'fp32_strict' keeps it IEEE-exact (== oracle).
-        const bool wino_on = !lowp_on && behind && (h->decoder_math == 0 || h->decoder_math == 3) &&
-                             (o.up2 ? femasr_conv_wino_up2_shape_ok_lim(&a, h->wino_log2_total, h->wino_log2_image)
-                                    : femasr_conv_wino_shape_ok_lim(&a, h->wino_log2_total, h->wino_log2_image));
-        // linear_math 1 (round 6): a 3x3 stride-1 conv in FRONT of a lookup (encoder ResBlocks, the conv behind every RSTB) runs as the
-        // split-bf16 GEMM over K = 9 Cin - the arithmetic of the linear layers (oracle: conv3x3_bf16s).  Its GroupNorm + SiLU prologue
-        // becomes a pass of its own (the GEMM takes plain rows), and it emits no GroupNorm partials: the next GroupNorm runs the
-        // stand-alone moments kernel, which gives the same coefficients bit for bit.
-        bool split3 = false;
-        {
-            femasr_conv_args q = a;
-            q.prologue = FEMASR_PRO_NONE;
-            split3 = h->linear_math == 1 && !behind && o.ksz == 3 && !lowp_on && !wino_on && !o.in_add &&
-                     (o.pro == FEMASR_PRO_NONE || o.pro == FEMASR_PRO_GN_SILU) && femasr_conv3x3_bf16s_shape_ok(&q);
-        }
-        float *act_tmp = nullptr;
-        if (split3 && o.pro == FEMASR_PRO_GN_SILU) act_tmp = alloc_f(x.numel());
-        const bool gn_ok = split3 ? false : lowp_on ? (cout % 32 == 0 && cout / 32 <= 8 && ((cout / 32) & (cout / 32 - 1)) == 0)
-                                   : (femasr_conv_halo_eligible(&a) && femasr_gn_fusable(cout));
-        if (o.want_gn && gn_ok) {
-            // exact x2 convs (phase filters) emit one partial per half-resolution tile and phase
-            // (a Winograd conv emits one partial per 16x16-pixel sub-block, orc_gn_coeffs mode 2)
-            y.gn_tiles = wino_on ? femasr_conv_wino_gn_tiles(Ho, Wo)
-                         : ((o.up2 && !lowp_on) ? 4 * ((x.H + 7) / 8) * ((x.W + 15) / 16) : ((Ho + 7) / 8) * ((Wo + 15) / 16));
+        a.act = o.act; a.res1 = o.res1; a.res2 = o.res2; a.in_add = o.in_add;
+        a.Ho = (Hv + 2 * o.pad - o.ksz) / o.stride + 1; a.Wo = (Wv + 2 * o.pad - o.ksz) / o.stride + 1;
+        return a;
+    }
+
+    T conv(const T &x, const std::string &prefix, int cout, const ConvOpt &o)
+    {
+        femasr_conv_args a = conv_args(x, cout, o);
+        T y = alloc_t(x.B, a.Ho, a.Wo, cout);
+        a.out = y.p;
+        const ConvForm f = conv_form(h, h->modes, prefix, a);
+        if (o.in_add && f != CONV_WINO_UP2 && !rc)
+            rc = femasr_set_error(FEMASR_ERR_INVALID, "conv %s: a second input was scheduled for a conv that does not run in the x2 Winograd-type form", prefix.c_str());
+        // the split 3x3 form applies a GroupNorm + SiLU prologue as a pass of its own (exact SiLU: these convs feed the lookup)
+        float *act_tmp = (f == CONV_SPLIT && o.pro == FEMASR_PRO_GN_SILU) ? alloc_f(x.numel()) : nullptr;
+        if (o.want_gn && (y.gn_tiles = gn_tiles(f, a)) > 0) {
             y.gn_part = (double *)arena->alloc((size_t)x.B * y.gn_tiles * 32 * 2 * sizeof(double));
             if (!y.gn_part && !rc) rc = femasr_set_error(FEMASR_ERR_WORKSPACE, "workspace too small");
         }
         if (rc || dry()) { release(act_tmp); return y; }
-        a.w = Wt(prefix + ".weight"); a.bias = Wt(prefix + ".bias");
-        a.gn_part = y.gn_part;
-        if (o.up2) {
-            auto it = h->index.find(prefix + ".weight");
-            if (it != h->index.end()) a.w_up2 = h->specs[it->second].up2w;
-        }
+        const WSpec *w = spec(prefix + ".weight");
+        a.bias = Wt(prefix + ".bias");
         if (rc) { release(act_tmp); return y; }
-        if (split3 && act_tmp) {       // GroupNorm-apply + SiLU as its own pass (exact SiLU: these convs feed the lookup)
+        a.w = w->dev; a.gn_part = y.gn_part;
+        if (o.up2) a.w_up2 = w->up2w;
+        const void *image = a.w;
+        switch (f) {
+        case CONV_BF16X3: image = a.w_bf16x3 = w->bf16x3; break;
+        case CONV_WINO:
+        case CONV_WINO_UP2: image = a.w_wino = w->wino; a.fast_act = h->modes.decoder_math == 0 ? 1 : 0; break;
+        case CONV_SPLIT: image = a.w_bf16s = w->bf16s; break;
+        default: break;
+        }
+        if (!image) {       // (femasr_set_weight packs the images of every form layer_forms allows)
+            rc = femasr_set_error(FEMASR_ERR_WEIGHT, "internal: conv %s: the weights of its form %d were not packed", prefix.c_str(), (int)f);
+            release(act_tmp);
+            return y;
+        }
+        if (act_tmp) {
             Scope sa(h, s(), dry(), SLOT_GN, 0.0, (double)x.numel() * 8.0);
             const int ra = femasr_gn_silu_apply(s(), x.p, x.B, x.H, x.W, x.C, o.pa, o.pb, act_tmp);
             if (ra && !rc) rc = ra;
@@ -445,55 +496,9 @@ struct Ctx {
             a.prologue = FEMASR_PRO_NONE; a.pro_a = nullptr; a.pro_b = nullptr;
         }
         Scope sc(h, s(), dry(), 0, 0.0, 0.0);
-        int variant = 0; double flops = 0;
-        int r;
-        const float *wino_w = nullptr;
-        if (wino_on) {
-            auto it = h->index.find(prefix + ".weight");
-            if (it != h->index.end()) wino_w = h->specs[it->second].wino;
-        }
-        if (o.in_add && !(wino_on && o.up2)) {
-            rc = femasr_set_error(FEMASR_ERR_INVALID, "conv %s: a second input was scheduled for a conv that does not run in the x2 Winograd-type form", prefix.c_str());
-            return y;
-        }
-        if (wino_on && !wino_w) {
-            // the plan sized gn_part for the Winograd form (one partial per 16x16 sub-block); the direct kernels write 2-4x as many:
-            // never fall through to them - set_weight packs the Winograd weights for exactly these shapes
-            rc = femasr_set_error(FEMASR_ERR_WEIGHT, "conv %s: planned in the Winograd form but its weights were not packed for it", prefix.c_str());
-            return y;
-        }
-        const void *lin3 = nullptr;
-        if (h->linear_math == 1 && (split3 || (o.ksz == 1 && femasr_gemm_bf16s_shape_ok(&a)))) {
-            auto it = h->index.find(prefix + ".weight");
-            if (it != h->index.end()) lin3 = h->specs[it->second].lin3;
-        }
-        if (split3 && !lin3) {
-            rc = femasr_set_error(FEMASR_ERR_WEIGHT, "conv %s: planned as the split-bf16 GEMM but its weight planes were not packed", prefix.c_str());
-            release(act_tmp);
-            return y;
-        }
-
-        if (lin3) {
-            r = femasr_gemm_bf16s_launch(s(), &a, lin3, &variant, &flops);
-            variant += femasr_conv_variant_count() + femasr_conv_bf16x3_variant_count() + femasr_conv_wino_variant_count() + 1;
-        } else if (lowp_on) {
-            a.w_bf16x3 = split;
-            r = femasr_conv_bf16x3_launch(s(), &a, &variant, &flops);
-            variant += femasr_conv_variant_count();
-        } else if (wino_w) {
-            a.w_wino = wino_w;
-            a.fast_act = h->decoder_math == 0 ? 1 : 0;
-            if (o.up2) {
-                r = femasr_conv_wino_up2_launch(s(), &a, &flops);
-                variant = femasr_conv_wino_variant_count();          // the slot behind the F(4x4,3x3) variants
-            } else {
-                r = femasr_conv_wino_launch(s(), &a, &variant, &flops);
-            }
-            variant += femasr_conv_variant_count() + femasr_conv_bf16x3_variant_count();
-        } else {
-            r = femasr_conv2d_launch(s(), &a, nullptr, &variant, &flops);
-        }
-        sc.set_slot(SLOT_SMALL_COUNT + variant);
+        int slot = 0; double flops = 0;
+        const int r = femasr_conv_form_launch(s(), f, &a, &slot, &flops);
+        sc.set_slot(SLOT_SMALL_COUNT + slot);
         sc.set_flops(flops);
         // algorithmic bytes of the launch: every operand once - input (+ a second input), residuals, output, weights
         sc.set_bytes(4.0 * ((double)x.numel() * (o.in_add ? 2 : 1) + (double)y.numel() * (1 + (o.res1 ? 1 : 0) + (o.res2 ? 1 : 0)) +
@@ -531,16 +536,16 @@ struct Ctx {
     }
 
     // fema_utils.py:65-84 (+ optional fused `x + enc_feats[i]`, femasr_arch.py:361-362)
-    T resblock(T x, const std::string &p, const float *res2, bool free_x, bool lowp = false, bool out_gn = false)
+    T resblock(T x, const std::string &p, const float *res2, bool free_x, bool out_gn = false)
     {
         const size_t bc = (size_t)x.B * x.C;
         float *ab = gn(x, p + ".conv.0.norm");
-        ConvOpt o1; o1.pro = FEMASR_PRO_GN_SILU; o1.pa = ab; o1.pb = ab ? ab + bc : nullptr; o1.lowp = lowp; o1.want_gn = true;
+        ConvOpt o1; o1.pro = FEMASR_PRO_GN_SILU; o1.pa = ab; o1.pb = ab ? ab + bc : nullptr; o1.want_gn = true;
         T u = conv(x, p + ".conv.2", x.C, o1);
         release(ab);
         float *ab2 = gn(u, p + ".conv.3.norm");
         ConvOpt o2; o2.pro = FEMASR_PRO_GN_SILU; o2.pa = ab2; o2.pb = ab2 ? ab2 + bc : nullptr;
-        o2.res1 = x.p; o2.res2 = res2; o2.lowp = lowp; o2.want_gn = out_gn;
+        o2.res1 = x.p; o2.res2 = res2; o2.want_gn = out_gn;
         T y = conv(u, p + ".conv.5", x.C, o2);
         release(ab2);
         release(u);
@@ -609,23 +614,12 @@ struct Ctx {
         return x;
     }
 
-    // Will the x2 conv of a decoder stage with this input run in the Winograd-type form (the same test conv() makes)?  Then the skip
-    // feature of that stage is added by ITS staging (in_add) instead of by the previous stage's last epilogue (a second residual operand).
-    bool up2_wino_ok(const std::string &prefix, int B, int H, int W, int Cin, int Cout) const
+    T up_block(const T &x, const std::string &p, int cout, const float *res2_last, const float *in_add = nullptr)   // Upsample x2 -> conv -> RB -> RB
     {
-        if (!behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, prefix)) return false;
-        femasr_conv_args a{};
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.ksz = 3; a.stride = 1; a.pad = 1; a.up2 = 1;
-        a.prologue = FEMASR_PRO_NONE; a.act = FEMASR_ACT_NONE; a.Ho = 2 * H; a.Wo = 2 * W;
-        return (h->decoder_math == 0 || h->decoder_math == 3) && femasr_conv_wino_up2_shape_ok_lim(&a, h->wino_log2_total, h->wino_log2_image);
-    }
-
-    T up_block(const T &x, const std::string &p, int cout, const float *res2_last, bool lowp = false, const float *in_add = nullptr)   // Upsample x2 -> conv -> RB -> RB
-    {
-        ConvOpt o; o.up2 = 1; o.lowp = lowp; o.want_gn = true; o.in_add = in_add;
+        ConvOpt o; o.up2 = 1; o.want_gn = true; o.in_add = in_add;
         T c = conv(x, p + ".1", cout, o);
-        T r1 = resblock(c, p + ".2", nullptr, true, lowp, true);
-        return resblock(r1, p + ".3", res2_last, true, lowp, false);
+        T r1 = resblock(c, p + ".2", nullptr, true, true);
+        return resblock(r1, p + ".3", res2_last, true, false);
     }
 };
 
@@ -742,8 +736,7 @@ int run_tail(Ctx &c, T x, std::vector<T> &feats, bool fuse_skip, bool with_encod
                 }
                 c.release(prev_q);
             }
-            Ctx::ConvOpt oa; oa.lowp = true;
-            x = c.conv(ain, "after_quant_group." + qs + ".conv", channels_at(cfg.codebook_scale[q]), oa);
+            x = c.conv(ain, "after_quant_group." + qs + ".conv", channels_at(cfg.codebook_scale[q]), Ctx::ConvOpt{});
             if (ain.p != qv.p) c.release(ain);
             bool later = false;                             // is this z_quant combined into a later scale?
             for (int k = i + 1; k < h->max_depth; ++k) later = later || quant_at(h, k, nullptr);
@@ -754,17 +747,19 @@ int run_tail(Ctx &c, T x, std::vector<T> &feats, bool fuse_skip, bool with_encod
         // two-residual epilogue was the slowest instantiation of the F(4x4) kernel); otherwise folded into this block's last epilogue
         const bool next_skip = with_encoder && fuse_skip && i + 1 < h->max_depth && !quant_at(h, i + 1, nullptr);
         const int cout_i = channels_at(r * 2);
-        const bool skip_by_next = next_skip && c.up2_wino_ok("decoder_group." + std::to_string(i + 1) + ".block.1", x.B, 2 * x.H, 2 * x.W, cout_i, channels_at(r * 4));
+        T nx; nx.B = x.B; nx.H = 2 * x.H; nx.W = 2 * x.W; nx.C = cout_i;      // the input of the next stage's x2 conv
+        Ctx::ConvOpt ou; ou.up2 = 1;
+        const bool skip_by_next = next_skip && conv_form(h, h->modes, "decoder_group." + std::to_string(i + 1) + ".block.1",
+                                                         c.conv_args(nx, channels_at(r * 4), ou)) == CONV_WINO_UP2;
         const float *skip = (next_skip && !skip_by_next) ? feats[i + 1].p : nullptr;
-        T y = c.up_block(x, "decoder_group." + std::to_string(i) + ".block", cout_i, skip, true, pending_add.p);
+        T y = c.up_block(x, "decoder_group." + std::to_string(i) + ".block", cout_i, skip, pending_add.p);
         c.release(x);
         if (pending_add.p) { c.release(pending_add); pending_add = T{}; }
         if (next_skip) { if (skip_by_next) pending_add = feats[i + 1]; else c.release(feats[i + 1]); }
         x = y;
         prev_dec = x;
     }
-    Ctx::ConvOpt oo; oo.lowp = true;
-    T img = c.conv(x, "out_conv", 3, oo);
+    T img = c.conv(x, "out_conv", 3, Ctx::ConvOpt{});
     c.release(x);
     if (!c.rc && !c.dry()) {
         Scope sc(h, c.s(), c.dry(), SLOT_LAYOUT, 0.0, (double)img.B * 3.0 * crop_h * crop_w * 8.0);
@@ -810,7 +805,7 @@ int run_forward(femasr_handle *h, Arena *arena, hipStream_t stream, const float 
         Ctx::ConvOpt od; od.stride = 2;
         T d = c.conv(t, p + ".0", channels_at(res / 2), od);
         if (!t_kept) c.release(t);
-        t = c.resblock(d, p + ".1", nullptr, true, false, true);
+        t = c.resblock(d, p + ".1", nullptr, true, true);
         t = c.resblock(t, p + ".2", nullptr, true);
         res /= 2;
         t_kept = false;
@@ -827,7 +822,7 @@ int run_forward(femasr_handle *h, Arena *arena, hipStream_t stream, const float 
         int last = 0;                 // up-blocks nobody reads are skipped (the reference computes and discards them)
         for (int u = 1; u <= 2 && u < h->max_depth; ++u) if (needed(u)) last = u;
         for (int u = 0; u < last; ++u, ++bi) {
-            feats[u + 1] = c.up_block(feats[u], enc + ".blocks." + std::to_string(bi), channels_at(res * 2), nullptr, true);
+            feats[u + 1] = c.up_block(feats[u], enc + ".blocks." + std::to_string(bi), channels_at(res * 2), nullptr);
             res *= 2;
         }
         for (int u = 1; u < last; ++u)
@@ -853,8 +848,7 @@ int run_decode_indices(femasr_handle *h, Arena *arena, hipStream_t stream, const
         const int r = femasr_codebook_gather(c.s(), indices, (int64_t)B * hq * wq, cfg.e_dim[0], c.Wt("quantize_group.0.embedding.weight"), cfg.n_e[0], zq.p);
         if (r) c.rc = r;
     }
-    Ctx::ConvOpt oa; oa.lowp = true;
-    T x = c.conv(zq, "after_quant_group.0.conv", channels_at(cfg.codebook_scale[0]), oa);
+    T x = c.conv(zq, "after_quant_group.0.conv", channels_at(cfg.codebook_scale[0]), Ctx::ConvOpt{});
     c.release(zq);
     std::vector<T> feats(FEMASR_MAX_CODEBOOKS + 1);
     return run_tail(c, x, feats, false, false, nullptr, out_nchw, hq << h->max_depth, wq << h->max_depth);
@@ -905,15 +899,12 @@ int femasr_create(const femasr_config *cfg, femasr_handle **out)
     if (!guard.ok) { delete h; return femasr_set_error(FEMASR_ERR_HIP, "hipSetDevice(%d) failed", cfg->device); }
     const int rc = build_specs(h);
     if (rc) { delete h; return rc; }
-    const int nslots = SLOT_SMALL_COUNT + femasr_conv_variant_count() + femasr_conv_bf16x3_variant_count() + femasr_conv_wino_variant_count() + 1 +
-                       femasr_gemm_bf16s_variant_count();
-    h->acc_ms.assign(nslots, 0.0); h->acc_flops.assign(nslots, 0.0); h->acc_bytes.assign(nslots, 0.0); h->acc_n.assign(nslots, 0);
+    // profile slots: the small-kernel families, then every variant of every conv form in ConvForm order (femasr_conv_form_launch)
     for (int i = 0; i < SLOT_SMALL_COUNT; ++i) h->slot_names.push_back(kSmallNames[i]);
-    for (int i = 0; i < femasr_conv_variant_count(); ++i) h->slot_names.push_back(femasr_conv_variant_name(i));
-    for (int i = 0; i < femasr_conv_bf16x3_variant_count(); ++i) h->slot_names.push_back(femasr_conv_bf16x3_variant_name(i));
-    for (int i = 0; i < femasr_conv_wino_variant_count(); ++i) h->slot_names.push_back(femasr_conv_wino_variant_name(i));
-    h->slot_names.push_back(femasr_conv_wino_up2_variant_name());
-    for (int i = 0; i < femasr_gemm_bf16s_variant_count(); ++i) h->slot_names.push_back(femasr_gemm_bf16s_variant_name(i));
+    for (int f = 0; f < CONV_FORM_COUNT; ++f)
+        for (int v = 0; v < femasr_conv_form_variant_count((ConvForm)f); ++v) h->slot_names.push_back(femasr_conv_form_variant_name((ConvForm)f, v));
+    const size_t nslots = h->slot_names.size();
+    h->acc_ms.assign(nslots, 0.0); h->acc_flops.assign(nslots, 0.0); h->acc_bytes.assign(nslots, 0.0); h->acc_n.assign(nslots, 0);
     *out = h;
     return FEMASR_OK;
 }
@@ -921,7 +912,8 @@ int femasr_create(const femasr_config *cfg, femasr_handle **out)
 void femasr_destroy(femasr_handle *h)
 {
     if (!h) return;
-    for (auto &w : h->specs) { if (w.dev) (void)hipFree(w.dev); if (w.split) (void)hipFree(w.split); if (w.up2w) (void)hipFree(w.up2w); if (w.wino) (void)hipFree(w.wino); if (w.lin3) (void)hipFree(w.lin3); }
+    for (auto &w : h->specs)
+        for (void *p : {(void *)w.dev, (void *)w.up2w, w.bf16x3, (void *)w.wino, w.bf16s}) if (p) (void)hipFree(p);
     for (int q = 0; q < FEMASR_MAX_CODEBOOKS; ++q) {
         if (h->cbT[q]) (void)hipFree(h->cbT[q]);
         if (h->ee[q]) (void)hipFree(h->ee[q]);
@@ -961,52 +953,30 @@ int femasr_set_weight(femasr_handle *h, const char *key, const float *dev_ptr, c
     bool same = (ndim == w.ndim);
     for (int i = 0; same && i < ndim; ++i) same = (shape[i] == w.shape[i]);
     if (!same) return femasr_set_error(FEMASR_ERR_WEIGHT, "set_weight: shape mismatch for '%s'", key);
-    const size_t n = w.numel();
-    size_t alloc = n;
-    if (w.kind == W_CONV) alloc = femasr_packed_weight_floats((int)w.shape[0], (int)w.shape[1], (int)w.shape[2], (int)w.shape[3]);
-    if (w.kind == W_LINEAR) alloc = femasr_packed_weight_floats((int)w.shape[0], (int)w.shape[1], 1, 1);
-    if (!w.dev) FEMASR_CHECK_HIP(hipMalloc((void **)&w.dev, alloc * sizeof(float)));
-    int rc = FEMASR_OK;
-    if (w.kind == W_CONV)
-        rc = femasr_repack_oihw(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], (int)w.shape[2], (int)w.shape[3], w.dev);
-    else if (w.kind == W_LINEAR)
-        rc = femasr_repack_oihw(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], 1, 1, w.dev);
-    else
-        FEMASR_CHECK_HIP(hipMemcpyAsync(w.dev, dev_ptr, n * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
-    if (rc) return rc;
-    // (the encoder's two up-blocks only produce the decoder's skip features, femasr_arch.py:314,361-362: one-codebook networks count them)
-    const bool dec_side = behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, k);
-    if ((w.kind == W_LINEAR || (w.kind == W_CONV && w.shape[2] == 1 && w.shape[3] == 1)) && (w.shape[1] % 64) == 0) {
-        // 1x1 convs / nn.Linear: the three bf16 planes for the fp32-grade product on the bf16 matrix pipe (kernels_gemm_bf16.hip)
-        if (!w.lin3) FEMASR_CHECK_HIP(hipMalloc(&w.lin3, femasr_packed_weight_bf16s_bytes((int)w.shape[0], (int)w.shape[1])));
-        rc = femasr_repack_k1_bf16s(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], w.lin3);
-        if (rc) return rc;
-    }
-    if (w.kind == W_CONV && !dec_side && !w.up2 && w.shape[2] == 3 && w.shape[3] == 3 && (w.shape[1] % 64) == 0) {
-        // a 3x3 conv in FRONT of a codebook lookup (stride 1 or 2): the planes of its (9 Cin x Cout) implicit-GEMM matrix (round 6: linear_math 1
-        // runs it as the split-bf16 GEMM)
-        if (!w.lin3) FEMASR_CHECK_HIP(hipMalloc(&w.lin3, femasr_packed_weight_conv3x3_bf16s_bytes((int)w.shape[0], (int)w.shape[1])));
-        rc = femasr_repack_oihw_bf16s(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], w.lin3);
-        if (rc) return rc;
-    }
-    if (w.kind == W_CONV && w.up2 && w.shape[2] == 3 && w.shape[3] == 3 && (w.shape[1] % 32) == 0) {
-        if (!w.up2w) FEMASR_CHECK_HIP(hipMalloc((void **)&w.up2w, femasr_up2_weight_floats((int)w.shape[0], (int)w.shape[1]) * sizeof(float)));
-        rc = femasr_repack_oihw_up2(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], w.up2w);
-        if (rc) return rc;
-    }
-    if (w.kind == W_CONV && dec_side && w.shape[2] == 3 && w.shape[3] == 3 && (w.shape[1] % 32) == 0 &&
-        (w.shape[0] % 64) == 0) {
-        // Winograd-domain weights: F(4x4,3x3) for the plain convs, the 25-component form for the convs behind nn.Upsample(x2)
-        const size_t nf = w.up2 ? femasr_wino_up2_weight_floats((int)w.shape[0], (int)w.shape[1]) : femasr_wino_weight_floats((int)w.shape[0], (int)w.shape[1]);
-        if (!w.wino) FEMASR_CHECK_HIP(hipMalloc((void **)&w.wino, nf * sizeof(float)));
-        rc = w.up2 ? femasr_repack_oihw_wino_up2(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], w.wino)
-                   : femasr_repack_oihw_wino(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], w.wino);
-        if (rc) return rc;
-    }
-    if (w.kind == W_CONV && dec_side && w.shape[2] == 3 && w.shape[3] == 3 && (w.shape[1] % 32) == 0) {
-        const size_t nb = femasr_packed_weight_bf16x3_bytes((int)w.shape[0], (int)w.shape[1], 3, 3);
-        if (!w.split) FEMASR_CHECK_HIP(hipMalloc(&w.split, nb));
-        rc = femasr_repack_oihw_bf16x3(nullptr, dev_ptr, (int)w.shape[0], (int)w.shape[1], 3, 3, w.split);
+    if (w.kind != W_CONV && w.kind != W_LINEAR) {
+        if (!w.dev) FEMASR_CHECK_HIP(hipMalloc((void **)&w.dev, w.numel() * sizeof(float)));
+        FEMASR_CHECK_HIP(hipMemcpyAsync(w.dev, dev_ptr, w.numel() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+    } else {        // conv / linear: the weights of every form the layer can take
+        const int O = (int)w.shape[0], I = (int)w.shape[1], kk = w.kind == W_CONV ? (int)w.shape[2] : 1;      // (square kernels)
+        const std::array<bool, CONV_FORM_COUNT> can = layer_forms(h, w);
+        if (!w.dev) FEMASR_CHECK_HIP(hipMalloc((void **)&w.dev, femasr_packed_weight_floats(O, I, kk, kk) * sizeof(float)));
+        int rc = femasr_repack_oihw(nullptr, dev_ptr, O, I, kk, kk, w.dev);                  // CONV_DIRECT (every layer)
+        if (!rc && w.up2 && femasr_up2_weight_floats(O, I)) {       // ... of an x2 conv on the halo kernels: its phase matrices too
+            if (!w.up2w) FEMASR_CHECK_HIP(hipMalloc((void **)&w.up2w, femasr_up2_weight_floats(O, I) * sizeof(float)));
+            rc = femasr_repack_oihw_up2(nullptr, dev_ptr, O, I, w.up2w);
+        }
+        if (!rc && can[CONV_BF16X3]) {
+            if (!w.bf16x3) FEMASR_CHECK_HIP(hipMalloc(&w.bf16x3, femasr_packed_weight_bf16x3_bytes(O, I, 3, 3)));
+            rc = femasr_repack_oihw_bf16x3(nullptr, dev_ptr, O, I, 3, 3, w.bf16x3);
+        }
+        if (!rc && (can[CONV_WINO] || can[CONV_WINO_UP2])) {
+            if (!w.wino) FEMASR_CHECK_HIP(hipMalloc((void **)&w.wino, (w.up2 ? femasr_wino_up2_weight_floats(O, I) : femasr_wino_weight_floats(O, I)) * sizeof(float)));
+            rc = w.up2 ? femasr_repack_oihw_wino_up2(nullptr, dev_ptr, O, I, w.wino) : femasr_repack_oihw_wino(nullptr, dev_ptr, O, I, w.wino);
+        }
+        if (!rc && can[CONV_SPLIT]) {       // the three bf16 planes of the (K x Cout) matrix: K = Cin (1x1 / nn.Linear) or 9 Cin (3x3)
+            if (!w.bf16s) FEMASR_CHECK_HIP(hipMalloc(&w.bf16s, kk == 1 ? femasr_packed_weight_bf16s_bytes(O, I) : femasr_packed_weight_conv3x3_bf16s_bytes(O, I)));
+            rc = kk == 1 ? femasr_repack_k1_bf16s(nullptr, dev_ptr, O, I, w.bf16s) : femasr_repack_oihw_bf16s(nullptr, dev_ptr, O, I, w.bf16s);
+        }
         if (rc) return rc;
     }
     FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
@@ -1240,8 +1210,8 @@ int femasr_decode_indices(femasr_handle *h, void *stream, const int64_t *indices
 int femasr_set_decoder_math(femasr_handle *h, int mode)
 {
     FEMASR_REQUIRE(h && mode >= 0 && mode <= 3, "set_decoder_math: mode must be 0 (fp32), 1 (bf16x3), 2 (fp32, direct convs only) or 3 (fp32, exact SiLU)");
-    if (h->decoder_math != mode) h->plans.clear();
-    h->decoder_math = mode;
+    if (h->modes.decoder_math != mode) h->plans.clear();
+    h->modes.decoder_math = mode;
     return FEMASR_OK;
 }
 
@@ -1249,8 +1219,8 @@ int femasr_debug_set_wino_limits(femasr_handle *h, int log2_total, int log2_imag
 {
     FEMASR_REQUIRE(h && log2_total >= 0 && log2_total <= FEMASR_WINO_LOG2_TOTAL && log2_image >= 0 && log2_image <= FEMASR_WINO_LOG2_IMAGE,
                    "debug_set_wino_limits: exponents are 0 (default) or up to %d / %d", FEMASR_WINO_LOG2_TOTAL, FEMASR_WINO_LOG2_IMAGE);
-    h->wino_log2_total = log2_total ? log2_total : FEMASR_WINO_LOG2_TOTAL;
-    h->wino_log2_image = log2_image ? log2_image : FEMASR_WINO_LOG2_IMAGE;
+    h->modes.wino_log2_total = log2_total ? log2_total : FEMASR_WINO_LOG2_TOTAL;
+    h->modes.wino_log2_image = log2_image ? log2_image : FEMASR_WINO_LOG2_IMAGE;
     h->plans.clear();
     return FEMASR_OK;
 }
@@ -1258,8 +1228,8 @@ int femasr_debug_set_wino_limits(femasr_handle *h, int log2_total, int log2_imag
 int femasr_set_linear_math(femasr_handle *h, int mode)
 {
     FEMASR_REQUIRE(h && (mode == 0 || mode == 1), "set_linear_math: mode must be 0 (fp32 MFMA chain) or 1 (bf16 three-term split)");
-    if (h->linear_math != mode) h->plans.clear();
-    h->linear_math = mode;
+    if (h->modes.linear_math != mode) h->plans.clear();
+    h->modes.linear_math = mode;
     return FEMASR_OK;
 }
 

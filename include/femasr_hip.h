@@ -193,7 +193,7 @@ typedef struct {
                              femasr_arch.py:361-362) right in front of that stage's x2 conv, so the sum never makes a pass of its own. */
     const void *w_bf16s;  /* optional (struct version 101): femasr_repack_k1_bf16s weights.  When non-NULL the layer - a 1x1 stride-1 conv /
                              nn.Linear with Cin % 64 == 0, no prologue (network_swinir.py:19-21,105-107,121,143; femasr_arch.py:298), or (round 6, weights from
-                             femasr_repack_oihw_bf16s) a 3x3 stride-1 pad-1 conv with Cin % 64 == 0, no prologue, no activation - runs on
+                             femasr_repack_oihw_bf16s) a 3x3 pad-1 conv of stride 1 or 2 with Cin % 64 == 0, no prologue, no activation - runs on
                              the bf16 matrix pipe as an fp32-GRADE product: both operands split exactly into three bf16 terms, the six
                              partial products of relative size >= 2^-16 accumulated in fp32 (two accumulators), ~3x closer to the fp64
                              result than the fp32 fmaf chain and bit-identical to oracle/femasr_oracle.c orc_linear_bf16s, which restates
@@ -300,7 +300,7 @@ int femasr_repack_oihw_up2(void *stream, const float *in, int O, int I, float *o
 size_t femasr_packed_weight_bf16s_bytes(int O, int I);
 int femasr_repack_k1_bf16s(void *stream, const float *w_oi, int O, int I, void *out);
 /* The same for a 3x3 conv weight (O, I, 3, 3), I % 64 == 0: the planes of the (9 I x O) matrix of the conv's implicit GEMM, k = (3 ky + kx) I + c.
- * With such weights in w_bf16s a 3x3 stride-1 pad-1 conv (no prologue, no activation; bias and residual operands as usual) runs as the
+ * With such weights in w_bf16s a 3x3 pad-1 conv of stride 1 or 2 (no prologue, no activation; bias and residual operands as usual) runs as the
  * split-bf16 GEMM over K = 9 Cin: the same arithmetic as the linear layers (oracle: conv3x3_bf16s = im2col + orc_linear_bf16s).  FeMaSRNet
  * (linear_math 'bf16_split') uses it for the 3x3 convs in FRONT of the codebook lookup - the encoder's ResBlocks (femasr_arch.py:150-164,
  * fema_utils.py:65-84) and the conv behind every RSTB (network_swinir.py:465). */
