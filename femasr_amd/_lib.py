@@ -42,9 +42,9 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 102      # femasr_version(): debug hooks in their own header, uint8 tile kernels (femasr_conv_args ends with w_bf16s)
+ABI_VERSION = 103      # femasr_version(): FEMASR_ACT_RELU, the femasr_lpips_* entry points (femasr_conv_args ends with w_bf16s)
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
-ACT_NONE, ACT_GELU = 0, 1
+ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
 # name -> (restype, argtypes); every symbol include/femasr_hip.h declares
 SIGNATURES = {
@@ -114,6 +114,16 @@ SIGNATURES = {
     'femasr_gn_silu_apply': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp]),
     'femasr_image_u8_to_f32': (c_int, [vp, vp, c_int, c_int, c_int, vp]),
     'femasr_image_f32_to_u8': (c_int, [vp, vp, c_int, c_int, c_int, vp]),
+    'femasr_lpips_create': (c_int, [c_int, c_int, ctypes.POINTER(vp)]),
+    'femasr_lpips_destroy': (None, [vp]),
+    'femasr_lpips_set_weight': (c_int, [vp, ctypes.c_char_p, vp, ctypes.POINTER(c_i64), c_int]),
+    'femasr_lpips_finalize_weights': (c_int, [vp]),
+    'femasr_lpips_workspace_bytes': (c_int, [vp, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_lpips_forward': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, vp, szt]),
+    'femasr_lpips_scale_input': (c_int, [vp, vp, vp, c_int, c_int, c_int, vp]),
+    'femasr_lpips_tap_partials': (c_int, [c_int, c_int]),
+    'femasr_lpips_tap': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp]),
+    'femasr_lpips_finalize': (c_int, [vp, vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), vp, vp]),
     'femasr_clock_probe': (c_int, [vp, c_int, vp]),
     'femasr_clock_probe_entries': (c_int, []),
 }

@@ -5,7 +5,7 @@
 //                 (nn.Upsample, femasr_arch.py:172,202) and fused GroupNorm-apply + SiLU (fema_utils.py:72-79)
 //   conv_igemm    the remaining general convs as an implicit GEMM: k4 in_conv, stride-2 convs, odd shapes
 //                 (1x1 convs / nn.Linear / the VQ distance matrix live in kernels_gemm.hip)
-//   both          bias, exact-erf GELU, up to two residual adds on store (fema_utils.py:82-83;
+//   both          bias, exact-erf GELU (conv_igemm) or ReLU (both; LPIPS backbones), up to two residual adds on store (fema_utils.py:82-83;
 //                 network_swinir.py:276-277,482; femasr_arch.py:361-362)
 //
 // Arithmetic: v_mfma_f32_32x32x2_f32 — exact fp32, and per output element ONE fmaf chain in the oracle's K
@@ -282,6 +282,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8) ? 4 : 2) void conv_ige
                 for (int r = 0; r < 16; ++r) {
                     float v = acc[i][j][r] + bv;
                     if (p.act == FEMASR_ACT_GELU) v = det_gelu(v);
+                    else if (p.act == FEMASR_ACT_RELU) v = v > 0.f ? v : 0.f;
                     if (NRES >= 1) v = v + rbuf[tl % DEPTH][0][r];
                     if (NRES >= 2) v = v + rbuf[tl % DEPTH][NRES >= 2 ? 1 : 0][r];
                     if (ok_l(i, j, r)) stg_u32(p.out + uoff(i, j, r), 4u * loff, v);
@@ -326,6 +327,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8) ? 4 : 2) void conv_ige
                     if (p.act == FEMASR_ACT_GELU) {         // two at a time on the packed fp32 ALU (bit-identical per element)
                         const det_f32x2 g0 = det_gelu2(det_f32x2{v[0], v[1]}), g1 = det_gelu2(det_f32x2{v[2], v[3]});
                         v[0] = g0[0]; v[1] = g0[1]; v[2] = g1[0]; v[3] = g1[1];
+                    } else if (p.act == FEMASR_ACT_RELU) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -532,7 +536,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8) ? 4 : 2) void conv3x3_
         __syncthreads();     // patch buffers swap: ONE barrier per 32-channel block (NTAP taps x 16 MFMA steps)
     }
 
-    // out = (acc + bias) + res1 + res2, in that order (bit-exact contract).  Address = uniform part (SGPRs) + one per-lane
+    // out = act(acc + bias) + res1 + res2 (act: none or ReLU), in that order (bit-exact contract).  Address = uniform part (SGPRs) + one per-lane
     // offset: element r of row tile i sits at pixel row 2*(wm*TM+i) + (r>>3), pixel column (r&3) + 8*((r>>2)&1) +
     // 4*(lane>>5) of the 8x16 tile.  Full tiles: residual loads are branch-free batches of one 32x32 tile issued one tile
     // ahead of the stores (see conv_igemm_kernel's epilogue for why).
@@ -591,6 +595,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8) ? 4 : 2) void conv3x3_
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[i][j][r] + bv;
+                if (p.act == FEMASR_ACT_RELU) v = v > 0.f ? v : 0.f;      // (uniform; the only activation of this kernel)
                 if (NRES >= 1) v = v + rbuf[tl % DEPTH][0][r];
                 if (NRES >= 2) v = v + rbuf[tl % DEPTH][NRES >= 2 ? 1 : 0][r];
                 if (ok_l(i, j, r)) {
@@ -839,7 +844,7 @@ extern "C" int femasr_conv_small_launch_blocks(int blocks)
 bool femasr_conv_halo_eligible(const femasr_conv_args *a)
 {
     return a->ksz == 3 && a->stride == 1 && a->pad == 1 && (a->Cin % BK) == 0 && a->prologue != FEMASR_PRO_LN &&
-           a->act == FEMASR_ACT_NONE && !(a->up2 && a->prologue != FEMASR_PRO_NONE) &&
+           (a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_RELU) && !(a->up2 && a->prologue != FEMASR_PRO_NONE) &&
            (size_t)a->B * a->H * a->W * a->Cin < ((size_t)1 << 31);
 }
 
@@ -856,8 +861,10 @@ int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq
     FEMASR_REQUIRE(a && a->in && a->w && a->B > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0,
                    "conv2d: null pointer or empty shape");
     FEMASR_REQUIRE(vq || (a->bias && a->out), "conv2d: bias/out must be set");
-    FEMASR_REQUIRE(a->ksz >= 1 && a->ksz <= 7 && (a->stride == 1 || a->stride == 2) && a->pad >= 0,
+    // (ksz 11 / stride 4: AlexNet's first conv, LPIPS; it runs on the generic-Cin implicit GEMM)
+    FEMASR_REQUIRE(a->ksz >= 1 && a->ksz <= 11 && (a->stride == 1 || a->stride == 2 || a->stride == 4) && a->pad >= 0,
                    "conv2d: unsupported ksz=%d stride=%d pad=%d", a->ksz, a->stride, a->pad);
+    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU || a->act == FEMASR_ACT_RELU, "conv2d: bad activation %d", a->act);
     FEMASR_REQUIRE(a->prologue == FEMASR_PRO_NONE || a->prologue == FEMASR_PRO_GN_SILU,
                    "conv2d: bad prologue %d (LayerNorm is a separate pass: femasr_layernorm)", a->prologue);
     const int Hv = a->up2 ? 2 * a->H : a->H, Wv = a->up2 ? 2 * a->W : a->W;
@@ -887,7 +894,7 @@ int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq
     p.NT32 = (a->Cout + 31) / 32;
     p.gn_part = a->gn_part;
     p.kperm = (a->ksz == 1 && vec) ? 1 : 0;       // weights packed by femasr_repack_oihw in the GEMM layout
-    if (femasr_conv_halo_eligible(a) && a->Cout == 3 && !a->up2 && a->prologue == FEMASR_PRO_NONE && !a->gn_part) {
+    if (femasr_conv_halo_eligible(a) && a->Cout == 3 && !a->up2 && a->prologue == FEMASR_PRO_NONE && a->act == FEMASR_ACT_NONE && !a->gn_part) {
         // out_conv: direct VALU kernel on the compact [k][4] weights stored behind the fragment-major matrix
         const size_t tail = femasr_compact_weight_floats(a->Cout, a->Cin, 3, 3);
         const float *wc = a->w + (size_t)p.nchunks * p.NT32 * 1024;

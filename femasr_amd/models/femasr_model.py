@@ -13,8 +13,11 @@ What is mirrored (same names, argument meaning and behaviour):
   extract_gt_indices       femasr_model.py:144-146  `net_hq(gt)` -> indices
 What is NOT here: training (optimizers, losses, discriminator, schedulers), best-model bookkeeping, tensorboard.
 Metrics: the reference evaluates them with `pyiqa` (not installed here): 'psnr' and 'ssim' follow the BasicSR
-definitions (crop_border, test_y_channel on the BT.601 Y of the uint8-rounded image); other types (lpips, ...) are
-reported as skipped.  There is no CPU path: the module needs a GPU and the HIP library.
+definitions (crop_border, test_y_channel on the BT.601 Y of the uint8-rounded image); 'lpips' (AlexNet) and 'lpips-vgg'
+(VGG16) are LPIPS v0.1 on the GPU (femasr_amd.lpips, csrc/lpips.hip) when their options carry `pretrained_model_path`
+(pyiqa's keyword; optionally `backbone_model_path`): scored on (sr_u8 / 255, gt) as femasr_model.py:262 does, the uint8 SR
+image never leaving the device.  Without a weight file (weights are never downloaded) they, like every other type (niqe,
+musiq, ...), are reported as skipped (None).  There is no CPU path: the module needs a GPU and the HIP library.
 """
 import logging
 import os
@@ -25,6 +28,7 @@ import numpy as np
 import torch
 
 from .. import imgproc
+from .. import lpips as lpips_metric
 from ..archs import build_network
 from . import MODEL_REGISTRY
 
@@ -165,16 +169,20 @@ class FeMaSRModel:
         val_opt = self.opt.get('val', {}) or {}
         metrics = val_opt.get('metrics') or {}
         self.metric_results = {name: 0.0 for name in metrics}
-        skipped = sorted(name for name, m in metrics.items() if m.get('type') not in _METRICS)
+        gpu_metrics = {name: self._gpu_metric(name, m) for name, m in metrics.items()
+                       if m.get('type') in lpips_metric.METRIC_NETS and m.get('pretrained_model_path')}
+        skipped = sorted(name for name, m in metrics.items() if m.get('type') not in _METRICS and name not in gpu_metrics)
         if skipped:
-            logger.warning('metrics %s need pyiqa (not installed): skipped', skipped)
+            logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), '
+                           'other pyiqa types are not implemented in this build', skipped)
         n = 0
         for val_data in dataloader:
             img_name = os.path.splitext(os.path.basename(val_data['lq_path'][0]))[0]
             self.feed_data(val_data)
             self.test()
             # tensor2img (img_util.py:38-94) on the GPU: clamp / x255 / round-half-even in a HIP kernel, uint8 crosses PCIe
-            sr_img = imgproc.output_to_u8(self.output).cpu().numpy()
+            sr_u8 = imgproc.output_to_u8(self.output)
+            sr_img = sr_u8.cpu().numpy()
             if save_img:
                 suffix = val_opt.get('suffix') or self.opt['name']
                 save_img_path = os.path.join(self.opt['path']['visualization'], dataset_name, f'{img_name}_{suffix}.png')
@@ -189,6 +197,11 @@ class FeMaSRModel:
                     fn = _METRICS.get(m.get('type'))
                     if fn is not None:
                         self.metric_results[name] += fn(sr_img, gt_img, **{k: v for k, v in m.items() if k not in ('type', 'better')})
+                if gpu_metrics:
+                    # metric_data = [img2tensor(sr_img).unsqueeze(0) / 255, self.gt] (femasr_model.py:262), the /255 in a HIP kernel
+                    sr = imgproc.u8_to_input(sr_u8)
+                    for name, fn in gpu_metrics.items():
+                        self.metric_results[name] += fn(sr, self.gt).item()
             del self.lq, self.output
             if hasattr(self, 'gt'):
                 del self.gt
@@ -198,6 +211,15 @@ class FeMaSRModel:
         if metrics:
             logger.info('Validation %s: %s', dataset_name, self.metric_results)
         return self.metric_results
+
+    def _gpu_metric(self, name, m):
+        """The LPIPS module of metric `name` (built once per model and option set)."""
+        cache = self.__dict__.setdefault('_lpips_metrics', {})
+        key = (name, m.get('type'), m.get('pretrained_model_path'), m.get('backbone_model_path'))
+        if key not in cache:
+            cache[key] = lpips_metric.create_metric(m['type'], device=self.device, pretrained_model_path=m['pretrained_model_path'],
+                                                    backbone_model_path=m.get('backbone_model_path'))
+        return cache[key]
 
     def get_current_visuals(self):
         out = OrderedDict(lq=self.lq.detach().cpu(), result=self.output.detach().cpu())

@@ -131,3 +131,18 @@ def synth_input(seed: int, shape, tag: str = 'input') -> np.ndarray:
                 + 0.1 * np.sin(17.0 * (yy + xx) + p[2])
     img = 0.7 * base + 0.3 * noise
     return np.clip(img, 0.0, 0.999).astype(np.float32)
+
+
+def lpips_state(shapes, seed: int = 0):
+    """Synthetic LPIPS weights for {canonical key: shape} (femasr_amd.lpips.expected_shapes): He-scaled conv weights (uniform with
+    variance 2 / fan_in), small positive biases (no tap's features die), non-negative heads in [0, 1) / C_k as the trained heads are."""
+    out = {}
+    for key, shape in shapes.items():
+        if key.startswith('lin'):
+            out[key] = (uniform(seed, key, shape, 0.0, 1.0) / shape[1]).astype(np.float32)
+        elif key.endswith('.bias'):
+            out[key] = uniform(seed, key, shape, 0.01, 0.1)
+        else:
+            lim = float(np.sqrt(6.0 / (shape[1] * shape[2] * shape[3])))
+            out[key] = uniform(seed, key, shape, -lim, lim)
+    return out

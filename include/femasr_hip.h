@@ -59,7 +59,7 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -136,7 +136,7 @@ int femasr_pad_nchw_to_nhwc(void *stream, const float *in, int B, int C, int H, 
 int femasr_crop_nhwc_to_nchw(void *stream, const float *in, int B, int Hs, int Ws, int C, int Hc, int Wc, float *out);
 
 enum { FEMASR_PRO_NONE = 0, FEMASR_PRO_GN_SILU = 1, FEMASR_PRO_LN = 2 /* retired: LayerNorm is femasr_layernorm, a separate pass */ };
-enum { FEMASR_ACT_NONE = 0, FEMASR_ACT_GELU = 1 };
+enum { FEMASR_ACT_NONE = 0, FEMASR_ACT_GELU = 1, FEMASR_ACT_RELU = 2 /* v > 0 ? v : +0 (LPIPS backbones; direct fp32 forms only) */ };
 
 /* Convolution / linear on fp32 MFMA.  Replaces nn.Conv2d (femasr_arch.py:150,159,173,
  * 203,273,298; fema_utils.py:75,78,90; network_swinir.py:465), nn.Upsample(x2) fused on load
@@ -154,7 +154,7 @@ typedef struct {
     const float *pro_a;   /* GN: a[B][Cin] */
     const float *pro_b;   /* GN: b[B][Cin] */
     const float *pro_c;   /* unused (was LN beta) */
-    int32_t act;          /* FEMASR_ACT_* (applied after bias, before residuals) */
+    int32_t act;          /* FEMASR_ACT_* (applied after bias, before residuals); RELU: the direct fp32 halo / implicit-GEMM forms only */
     const float *res1;    /* optional (B,Ho,Wo,Cout) added after act   */
     const float *res2;    /* optional second residual                   */
     float *out;           /* (B,Ho,Wo,Cout) */
@@ -332,6 +332,40 @@ int femasr_image_u8_to_f32(void *stream, const uint8_t *in_hwc, int H, int W, in
 /* fp32 CHW RGB -> clamp [0,1] -> (x*255).round() half-to-even -> uint8 HWC (swap_rb=1: BGR for cv2.imwrite).
  * Replaces tensor2img (basicsr/utils/img_util.py:38-94). */
 int femasr_image_f32_to_u8(void *stream, const float *in_chw, int H, int W, int swap_rb, uint8_t *out_hwc);
+
+/* ---- LPIPS v0.1 (inference): validation's key metric (pyiqa 'lpips' = AlexNet, 'lpips-vgg' = VGG16; femasr_model.py:27-34,262) ----
+ * A handle holds one backbone and its five linear heads.  Weight keys are canonical: net.sliceK.I.weight / .bias (K = 1..5, I = the
+ * torchvision `features` index: alex 0, 3, 6, 8, 10; vgg16 0, 2 | 5, 7 | 10, 12, 14 | 17, 19, 21 | 24, 26, 28) and linK.model.1.weight
+ * (K = 0..4, shape (1, C_k, 1, 1)).  set_weight copies (conv weights repacked by femasr_repack_oihw) and synchronises.  Every conv has
+ * a bias and a ReLU (FEMASR_ACT_RELU on the exact fp32 conv forms); the taps are the ReLU outputs of alex conv0/3/6/8/10 and vgg16
+ * relu1_2/2_2/3_3/4_3/5_3.  Minimum input: H, W >= 31 (alex) / 16 (vgg16), below that FEMASR_ERR_INVALID and nothing is launched;
+ * shapes whose largest feature tensor of the 2B-image batch reaches 2^31 elements are refused as well (split the batch). */
+typedef struct femasr_lpips_handle femasr_lpips_handle;
+int femasr_lpips_create(int net /* 0 alex, 1 vgg16 */, int device, femasr_lpips_handle **out);
+void femasr_lpips_destroy(femasr_lpips_handle *h);
+int femasr_lpips_set_weight(femasr_lpips_handle *h, const char *key, const float *dev_ptr, const int64_t *shape, int ndim);
+int femasr_lpips_finalize_weights(femasr_lpips_handle *h);     /* FEMASR_ERR_WEIGHT names the first missing key */
+int femasr_lpips_workspace_bytes(const femasr_lpips_handle *h, int B, int H, int W, size_t *bytes);
+/* x0, x1: (B,3,H,W) fp32 NCHW RGB in [0,1].  out[B] = lpips.LPIPS.forward(x0, x1, normalize=True) per pair; per_layer [B][5] the five
+ * spatially averaged tap terms (may be NULL).  `ws` >= femasr_lpips_workspace_bytes, 256-byte aligned. */
+int femasr_lpips_forward(femasr_lpips_handle *h, void *stream, const float *x0_nchw, const float *x1_nchw, int B, int H, int W,
+                         float *out, float *per_layer, void *ws, size_t ws_bytes);
+/* Per-op units of the forward (the same kernels; unit tests compose them):
+ * scale_input: x0, x1 (B,3,H,W) NCHW -> out (2B,H,W,3) NHWC, x0 in samples 0..B-1, x1 in B..2B-1; t = 2x - 1, then
+ *   (t - shift) / scale, shift = (-.030, -.088, -.188), scale = (.458, .448, .450) as fp32.
+ * tap: f (B2,H,W,C) NHWC ReLU features of the 2B-image batch (C % 64 == 0, 64..512), w_lin [C] the head.  For each pair b < B2/2 and
+ *   pixel: n = f / (sqrt(sum_c f^2) + 1e-10) for f[b] and f[b + B2/2], value = sum_c w_lin[c] (n0 - n1)^2 in fp32; one fp64 partial
+ *   sum per 32-pixel block: partials [B2/2][femasr_lpips_tap_partials(H, W)].  pool 1: max-pool 3x3 / 2, pool 2: 2x2 / 2 (no padding,
+ *   floor) of f into pooled_out (B2, Hp, Wp, C) in the same launch; pool 0: pooled_out unused.  Refused (nothing launched):
+ *   a map too small for the pool, more than 65535 pairs.
+ * finalize: partials of ntaps taps back to back (tap k: [B][femasr_lpips_tap_partials(tap_hw[2k], tap_hw[2k+1])]), tap_hw a HOST array
+ *   [ntaps][2] -> per_layer [B][ntaps] (sum / (H_k W_k) in fp64, rounded to fp32; may be NULL) and out[B] (the terms summed in tap
+ *   order in fp32).  Fixed summation order throughout, no atomics: deterministic and batch-invariant. */
+int femasr_lpips_scale_input(void *stream, const float *x0_nchw, const float *x1_nchw, int B, int H, int W, float *out_nhwc);
+int femasr_lpips_tap_partials(int H, int W);
+int femasr_lpips_tap(void *stream, const float *f, int B2, int H, int W, int C, const float *w_lin, int pool, float *pooled_out,
+                     double *partials);
+int femasr_lpips_finalize(void *stream, const double *partials, int B, int ntaps, const int32_t *tap_hw, float *out, float *per_layer);
 
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
