@@ -133,6 +133,7 @@ DEBUG_SIGNATURES = {
     'femasr_debug_mfma_bf16': (c_int, [vp, vp, vp, vp, c_int, vp]),
     'femasr_gemm_force_config': (c_int, [c_int]),
     'femasr_conv_small_launch_blocks': (c_int, [c_int]),
+    'femasr_debug_conv_variant_name': (c_int, [ctypes.POINTER(ConvArgs), ctypes.c_char_p, c_int]),
 }
 
 _lib = None

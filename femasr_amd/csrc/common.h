@@ -31,6 +31,7 @@ struct conv_vq_epilogue {
 };
 int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_epilogue *vq,
                          int *variant_out, double *flops_out);
+int femasr_conv2d_pick_variant(const femasr_conv_args *a);      // the variant femasr_conv2d_launch runs (no VQ epilogue); shape-only
 int femasr_conv_variant_count();
 const char *femasr_conv_variant_name(int v);
 bool femasr_conv_halo_eligible(const femasr_conv_args *a);      // 3x3 s1 p1, Cin % 32 == 0: the halo kernels
@@ -48,6 +49,7 @@ inline size_t femasr_compact_weight_floats(int O, int I, int kh, int kw)
 bool femasr_gemm_eligible(const femasr_conv_args *a);
 int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_epilogue *vq, int *variant_out, double *flops_out);
 int femasr_gemm_variant_count();
+int femasr_gemm_pick_variant(const femasr_conv_args *a, bool vq);
 const char *femasr_gemm_variant_name(int v);
 int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out);
 
@@ -56,6 +58,7 @@ bool femasr_gemm_bf16s_shape_ok(const femasr_conv_args *a);
 bool femasr_conv3x3_bf16s_shape_ok(const femasr_conv_args *a);      // the 3x3 pad-1 form (K = 9 Cin, stride 1 or 2) of the same kernel
 int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const void *w_bf16s, int *variant_out, double *flops_out);
 int femasr_gemm_bf16s_variant_count();
+int femasr_gemm_bf16s_pick_variant(const femasr_conv_args *a);
 const char *femasr_gemm_bf16s_variant_name(int v);
 
 // Winograd F(4x4,3x3) 3x3 convs (kernels_wino.hip)
@@ -65,6 +68,7 @@ bool femasr_conv_wino_shape_ok_lim(const femasr_conv_args *a, int log2_total, in
 int femasr_conv_wino_gn_tiles(int H, int W);      // fused GroupNorm partials of a Winograd conv: one per 16x16-pixel sub-block
 int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
 int femasr_conv_wino_variant_count();
+int femasr_conv_wino_pick_variant(const femasr_conv_args *a);
 const char *femasr_conv_wino_variant_name(int v);
 // nn.Upsample(x2) + 3x3 conv in the 25-product Winograd-type form (kernels_wino_up2.hip); GroupNorm partials per 16x16 OUTPUT sub-block
 bool femasr_conv_wino_up2_shape_ok(const femasr_conv_args *a);
@@ -77,6 +81,7 @@ bool femasr_conv_bf16x3_eligible(const femasr_conv_args *a);
 bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a);      // the same rule without the w_bf16x3 pointer (planner)
 int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
 int femasr_conv_bf16x3_variant_count();
+int femasr_conv_bf16x3_pick_variant(const femasr_conv_args *a);
 const char *femasr_conv_bf16x3_variant_name(int v);
 
 // The forms a conv runs in, in profile-slot order (femasr_create lays the slots out from this list)

@@ -855,6 +855,20 @@ const char *femasr_conv_variant_name(int v)
     return v >= 0 ? g_variants[v].name : "?";
 }
 
+// out_conv: the direct VALU kernel on the compact [k][4] weights (its own launcher branch)
+static bool conv_is_cout3(const femasr_conv_args *a)
+{
+    return femasr_conv_halo_eligible(a) && a->Cout == 3 && !a->up2 && a->prologue == FEMASR_PRO_NONE && a->act == FEMASR_ACT_NONE && !a->gn_part;
+}
+
+int femasr_conv2d_pick_variant(const femasr_conv_args *a)
+{
+    if (femasr_gemm_eligible(a)) return kNumVariants + femasr_gemm_pick_variant(a, false);
+    if (conv_is_cout3(a)) return kNumVariants - 1;
+    const int Hv = a->up2 ? 2 * a->H : a->H, Wv = a->up2 ? 2 * a->W : a->W;
+    return pick_variant(a, (Hv + 2 * a->pad - a->ksz) / a->stride + 1, (Wv + 2 * a->pad - a->ksz) / a->stride + 1);
+}
+
 int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_epilogue *vq,
                          int *variant_out, double *flops_out)
 {
@@ -894,7 +908,7 @@ int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq
     p.NT32 = (a->Cout + 31) / 32;
     p.gn_part = a->gn_part;
     p.kperm = (a->ksz == 1 && vec) ? 1 : 0;       // weights packed by femasr_repack_oihw in the GEMM layout
-    if (femasr_conv_halo_eligible(a) && a->Cout == 3 && !a->up2 && a->prologue == FEMASR_PRO_NONE && a->act == FEMASR_ACT_NONE && !a->gn_part) {
+    if (conv_is_cout3(a)) {
         // out_conv: direct VALU kernel on the compact [k][4] weights stored behind the fragment-major matrix
         const size_t tail = femasr_compact_weight_floats(a->Cout, a->Cin, 3, 3);
         const float *wc = a->w + (size_t)p.nchunks * p.NT32 * 1024;

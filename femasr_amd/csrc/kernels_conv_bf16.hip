@@ -611,6 +611,16 @@ bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a)
            (size_t)a->B * a->H * a->W * (a->up2 ? 4 : 1) * a->Cout < ((size_t)1 << 31);
 }
 
+int femasr_conv_bf16x3_pick_variant(const femasr_conv_args *a)
+{
+    int cls = a->Cout > 128 ? 3 : (a->Cout > 64 ? 0 : (a->Cout > 32 ? 1 : 2));
+#ifdef FEMASR_TAPTIME
+    if (getenv("FEMASR_BF16_CLS")) cls = atoi(getenv("FEMASR_BF16_CLS"));      // debug build only: force a tile class
+#endif
+    // Cout 33..64 uses the 4-wave 64 px x 32 ch tiling (rows 15..17: +2.5 % / +9 % fused-x2 over the 8-wave rows 3..5)
+    return (cls == 1 ? 15 : cls * 3) + (a->up2 ? 2 : a->prologue);
+}
+
 int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out)
 {
     FEMASR_REQUIRE(a && a->in && a->bias && a->out && femasr_conv_bf16x3_eligible(a), "conv bf16x3: not eligible");
@@ -621,12 +631,7 @@ int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *var
     p.in = a->in; p.bias = a->bias; p.pro_a = a->pro_a; p.pro_b = a->pro_b; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
     p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.ksz = 3; p.stride = 1; p.pad = 1; p.up2 = a->up2;
     p.Ho = Hv; p.Wo = Wv; p.NT32 = (a->Cout + 31) / 32;
-    int cls = a->Cout > 128 ? 3 : (a->Cout > 64 ? 0 : (a->Cout > 32 ? 1 : 2));
-#ifdef FEMASR_TAPTIME
-    if (getenv("FEMASR_BF16_CLS")) cls = atoi(getenv("FEMASR_BF16_CLS"));      // debug build only: force a tile class
-#endif
-    // Cout 33..64 uses the 4-wave 64 px x 32 ch tiling (rows 15..17: +2.5 % / +9 % fused-x2 over the 8-wave rows 3..5)
-    const int vi = (cls == 1 ? 15 : cls * 3) + (a->up2 ? 2 : a->prologue);
+    const int vi = femasr_conv_bf16x3_pick_variant(a);
     Variant16 &v = g_v16[vi];
     p.tilesX = (p.Wo + 15) / 16;
     p.tilesY = (p.Ho + 7) / 8;

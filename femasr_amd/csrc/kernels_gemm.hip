@@ -374,23 +374,13 @@ int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out)
     return FEMASR_OK;
 }
 
-int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_epilogue *vq, int *variant_out, double *flops_out)
+// the variant a launch runs: epilogue (VQ argmin / activation + residual operands) and block configuration
+int femasr_gemm_pick_variant(const femasr_conv_args *a, bool vq)
 {
-    FEMASR_REQUIRE(a && a->in && a->w && femasr_gemm_eligible(a), "gemm: layer is not a 1x1 / linear layer with Cin %% 32 == 0");
-    FEMASR_REQUIRE(vq || (a->bias && a->out), "gemm: bias/out must be set");
-    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm: bad activation %d", a->act);
     const long long M = (long long)a->B * a->H * a->W;
-    FEMASR_REQUIRE(a->Ho == a->H && a->Wo == a->W, "gemm: Ho/Wo mismatch");
-    FEMASR_REQUIRE(M > 0 && M < (1ll << 31) - 256, "gemm: bad row count");
-    GemmParams p{};
-    p.A = a->in; p.W = a->w; p.bias = a->bias; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.M = (int)M; p.N = a->Cout; p.K = a->Cin; p.nchunks = a->Cin / 32;
-    p.NT32 = (p.N + 31) / 32;
-    const int mb128 = (p.M + 127) / 128, nb128 = (p.N + 127) / 128;
+    const int mb128 = (int)((M + 127) / 128), nb128 = (a->Cout + 127) / 128;
     int vi;
     if (vq) {
-        FEMASR_REQUIRE(vq->zz && vq->ee && vq->part && vq->nblk == nb128 && (a->Cout % 32) == 0, "vq epilogue: bad args");
-        p.vq_zz = vq->zz; p.vq_ee = vq->ee; p.vq_part = vq->part; p.vq_nblk = vq->nblk;
         vi = 6;
     } else {
         const int nres = (a->res1 ? 1 : 0) + (a->res2 ? 1 : 0);
@@ -422,9 +412,28 @@ int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_e
         const bool small = tiles < (double)small_tiles || (e2 > e3 ? e2 : e3) * 100.0 < (double)tail_pct;
         cfg = (!vq && small) ? 2 : (e3 > e2 + 0.02 ? 1 : 0);
     }
-    const int bt = kTileOf[cfg];
+    return vi + cfg * kPerCfg;
+}
+
+int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_epilogue *vq, int *variant_out, double *flops_out)
+{
+    FEMASR_REQUIRE(a && a->in && a->w && femasr_gemm_eligible(a), "gemm: layer is not a 1x1 / linear layer with Cin %% 32 == 0");
+    FEMASR_REQUIRE(vq || (a->bias && a->out), "gemm: bias/out must be set");
+    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm: bad activation %d", a->act);
+    const long long M = (long long)a->B * a->H * a->W;
+    FEMASR_REQUIRE(a->Ho == a->H && a->Wo == a->W, "gemm: Ho/Wo mismatch");
+    FEMASR_REQUIRE(M > 0 && M < (1ll << 31) - 256, "gemm: bad row count");
+    GemmParams p{};
+    p.A = a->in; p.W = a->w; p.bias = a->bias; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
+    p.M = (int)M; p.N = a->Cout; p.K = a->Cin; p.nchunks = a->Cin / 32;
+    p.NT32 = (p.N + 31) / 32;
+    if (vq) {
+        FEMASR_REQUIRE(vq->zz && vq->ee && vq->part && vq->nblk == (p.N + 127) / 128 && (a->Cout % 32) == 0, "vq epilogue: bad args");
+        p.vq_zz = vq->zz; p.vq_ee = vq->ee; p.vq_part = vq->part; p.vq_nblk = vq->nblk;
+    }
+    const int vi = femasr_gemm_pick_variant(a, vq != nullptr);
+    const int bt = kTileOf[vi / kPerCfg];
     p.MB = (p.M + bt - 1) / bt; p.NB = (p.N + bt - 1) / bt;
-    vi += cfg * kPerCfg;
     GVariant &v = g_gv[vi];
     int dev = 0;
     FEMASR_CHECK_HIP(hipGetDevice(&dev));

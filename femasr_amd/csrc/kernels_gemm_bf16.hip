@@ -474,6 +474,13 @@ extern "C" int femasr_debug_mfma_bf16(void *stream, const uint16_t *a, const uin
     return FEMASR_OK;
 }
 
+// 1x1 / linear: 3 * GELU + residual operands; the 3x3 form: 6 + residual operands
+int femasr_gemm_bf16s_pick_variant(const femasr_conv_args *a)
+{
+    const int nres = (a->res1 ? 1 : 0) + (a->res2 ? 1 : 0), act = a->act == FEMASR_ACT_GELU ? 1 : 0;
+    return a->ksz == 3 ? 6 + nres : 3 * act + nres;
+}
+
 int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const void *w_bf16s, int *variant_out, double *flops_out)
 {
     FEMASR_REQUIRE(a && a->in && w_bf16s && femasr_gemm_bf16s_shape_ok(a), "gemm_bf16s: layer is neither a 1x1 / linear layer nor a 3x3 pad-1 conv of stride 1 or 2 with Cin %% 64 == 0");
@@ -490,8 +497,7 @@ int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const voi
     p.imH = a->H; p.imW = a->W; p.imHo = Ho; p.imWo = Wo; p.stride = a->stride; p.Cin = a->Cin; p.tapmul = ((1 << 20) + (a->Cin >> 5) - 1) / (a->Cin >> 5);
     p.NT32 = (p.N + 31) / 32;
     p.MB = (p.M + 127) / 128; p.NB = (p.N + 127) / 128;
-    const int nres = (a->res1 ? 1 : 0) + (a->res2 ? 1 : 0), act = a->act == FEMASR_ACT_GELU ? 1 : 0;
-    const int vi = conv ? 6 + nres : 3 * act + nres;
+    const int vi = femasr_gemm_bf16s_pick_variant(a);
     GSVariant &v = g_gsv[vi];
     int dev = 0;
     FEMASR_CHECK_HIP(hipGetDevice(&dev));

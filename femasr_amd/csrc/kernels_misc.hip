@@ -6,6 +6,7 @@
 #include "common.h"
 #include "detmath.h"
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -1204,12 +1205,40 @@ int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a
     return r;
 }
 
+// femasr_conv2d: the form whose weights are given
+static ConvForm conv2d_form(const femasr_conv_args *a)
+{
+    return !a ? CONV_DIRECT : a->w_bf16s ? CONV_SPLIT : a->w_bf16x3 ? CONV_BF16X3 : !a->w_wino ? CONV_DIRECT : a->up2 ? CONV_WINO_UP2 : CONV_WINO;
+}
+
+extern "C" int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *name, int cap)
+{
+    FEMASR_REQUIRE(a && name && cap > 0, "debug_conv_variant_name: bad args");
+    // the shape checks of femasr_conv2d_launch that the variant rules divide by
+    FEMASR_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && a->Cin > 0 && a->Cout > 0 && a->ksz >= 1 && a->ksz <= 11 &&
+                   (a->stride == 1 || a->stride == 2 || a->stride == 4) && a->pad >= 0,
+                   "debug_conv_variant_name: empty shape or unsupported ksz=%d stride=%d pad=%d", a->ksz, a->stride, a->pad);
+    const ConvForm f = conv2d_form(a);
+    int v = 0;
+    switch (f) {
+    case CONV_BF16X3: v = femasr_conv_bf16x3_pick_variant(a); break;
+    case CONV_WINO: v = femasr_conv_wino_pick_variant(a); break;
+    case CONV_WINO_UP2: v = 0; break;
+    case CONV_SPLIT: v = femasr_gemm_bf16s_pick_variant(a); break;
+    default: v = femasr_conv2d_pick_variant(a); break;
+    }
+    const char *s = femasr_conv_form_variant_name(f, v);
+    const size_t n = strlen(s);
+    FEMASR_REQUIRE(n < (size_t)cap, "debug_conv_variant_name: the name needs %zu bytes, the buffer holds %d", n + 1, cap);
+    memcpy(name, s, n + 1);
+    return FEMASR_OK;
+}
+
 extern "C" int femasr_conv2d(void *stream, const femasr_conv_args *a)
 {
     FEMASR_REQUIRE(!a || !a->in_add || (a->w_wino && a->up2 && !a->w_bf16x3 && !a->w_bf16s),
                    "conv2d: in_add is only taken by the x2 Winograd-type form (up2 = 1 with w_wino, no w_bf16x3 / w_bf16s)");
-    // the form whose weights are given
-    const ConvForm f = !a ? CONV_DIRECT : a->w_bf16s ? CONV_SPLIT : a->w_bf16x3 ? CONV_BF16X3 : !a->w_wino ? CONV_DIRECT : a->up2 ? CONV_WINO_UP2 : CONV_WINO;
+    const ConvForm f = conv2d_form(a);
     FEMASR_REQUIRE(f != CONV_SPLIT || femasr_gemm_bf16s_shape_ok(a),
                    "conv2d: w_bf16s given but the layer is neither a 1x1 stride-1 layer nor a 3x3 pad-1 conv of stride 1 or 2, with Cin %% 64 == 0 and no prologue");
     FEMASR_REQUIRE(f != CONV_BF16X3 || femasr_conv_bf16x3_eligible(a), "conv2d: w_bf16x3 given but the layer is not eligible for the bf16x3 path");

@@ -573,6 +573,12 @@ int femasr_conv_wino_variant_count() { return kNumW; }
 const char *femasr_conv_wino_variant_name(int v) { return v >= 0 && v < kNumW ? g_wv[v].name : "?"; }
 int femasr_conv_wino_gn_tiles(int H, int W) { return ((H + 15) / 16) * ((W + 15) / 16); }
 
+// index = 3 * (prologue form) + residual operands
+int femasr_conv_wino_pick_variant(const femasr_conv_args *a)
+{
+    return 3 * (a->prologue == FEMASR_PRO_GN_SILU ? (a->fast_act ? 2 : 1) : 0) + (a->res1 ? (a->res2 ? 2 : 1) : 0);
+}
+
 int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out)
 {
     FEMASR_REQUIRE(a && a->in && a->w_wino && a->bias && a->out && femasr_conv_wino_shape_ok(a), "conv_wino: bad arguments / shape");
@@ -594,7 +600,7 @@ int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *varia
     FEMASR_REQUIRE(a->res1 || !a->res2, "conv_wino: res2 without res1");
     FEMASR_REQUIRE(!a->in_add, "conv_wino: in_add is only taken by the x2 form");
     if (flops_out) *flops_out = 2.0 * (double)a->B * a->H * a->W * 9.0 * (double)a->Cin * (double)a->Cout;      // ALGORITHMIC, see below
-    const int vi = 3 * (gn ? (a->fast_act ? 2 : 1) : 0) + (a->res1 ? (a->res2 ? 2 : 1) : 0);
+    const int vi = femasr_conv_wino_pick_variant(a);
     WVariant &v = g_wv[vi];
     const size_t lds = wino_lds_bytes(a->Cin, gn);
     int dev = 0;

@@ -32,6 +32,13 @@ int femasr_gemm_force_config(int cfg);
  * partial-moment order).  Returns the previous threshold. */
 int femasr_conv_small_launch_blocks(int blocks);
 
+/* Writes to name[cap] the profile-slot name (femasr_profile_name) of the kernel instantiation femasr_conv2d would launch for these
+ * arguments: the form from the weight images given (as femasr_conv2d picks it), the variant from the shape, prologue, fast_act,
+ * activation, residual operands and the small-launch / GEMM block rules in force.  Reads no pointer's target and launches nothing.
+ * Fails if the name with its terminating zero does not fit.  tests/ map their fp64 cases to the slots a forward fills with it
+ * (tests/test_gpu_fp64_anchor.py). */
+int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *name, int cap);
+
 #ifdef __cplusplus
 }
 #endif

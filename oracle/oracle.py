@@ -541,6 +541,8 @@ class OracleNet:
                         (self.gt_res // 2 ** self.max_depth * 2 ** (i + 1)) not in self.cb_scales)
             x = self._decoder_block(x, i, res2=feats[i + 1] if nxt_skip else None)
             self._probe(f'dec{i}' + ('_plus_skip' if nxt_skip else ''), x)
+            if nxt_skip:        # the reference's dec{i} (hooked before the add) = dec{i}_plus_skip - dec{i}_skip
+                self._probe(f'dec{i}_skip', feats[i + 1])
             prev_dec = x
         wout, bout = self._conv_w('out_conv')
         out = conv2d(x, wout, bout, 3, 1, 1)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from femasr_amd import synth
-from helpers import (cfg_name_of, check_indices_near_tie, load_golden, oracle_net, probe_err, synth_weights)
+from helpers import (assert_golden_probes, cfg_name_of, check_indices_near_tie, load_golden, oracle_net, synth_weights)
 
 TOL = 1e-3
 
@@ -32,15 +32,14 @@ def test_test_path_matches_reference(name, linear_math):
     nbad, nacc = check_indices_near_tie(idx, g)
     assert nbad == 0, f'{nbad} index mismatches ({nacc} would be near-tie acceptable)'
     assert idx.dtype == np.int64 and idx.shape == g['vq_indices'].shape
-    for k, v in net.probes.items():
-        if 'probe_pos_' + k in g:
-            err, scale = probe_err(g, k, v)
-            assert err <= 2e-5 * max(scale, 1.0), (k, err, scale)
+    assert_golden_probes(g, net.probes, f'{name} {linear_math}')
 
 
 def test_hq_forward_matches_reference():
     g, net, x = _run('hq_small_trained')
+    net.probes = {}
     y, idx = net.forward(x)
+    assert_golden_probes(g, net.probes, 'hq_small_trained')
     assert np.abs(y - g['output']).max() < TOL
     assert np.array_equal(idx, g['vq_indices'])
 
@@ -66,8 +65,11 @@ def test_full_tile_128_matches_reference():
     in every run by the real image tests/test_oracle_golden_r2.py::test_cli_arithmetic_on_testset_png[png_chip] (ADVICE r5) and by every
     small fixture; the GPU suite runs this tile in the default."""
     import os
-    g, net, x = _run('x4_tile128_trained', 'bf16_split' if os.environ.get('FEMASR_SLOW_TESTS') == '1' else 'fp32')
+    lm = 'bf16_split' if os.environ.get('FEMASR_SLOW_TESTS') == '1' else 'fp32'
+    g, net, x = _run('x4_tile128_trained', lm)
+    net.probes = {}
     y, idx = net.test(x, return_indices=True)
+    assert_golden_probes(g, net.probes, f'x4_tile128_trained {lm}')
     st = int(g['out_stride'])
     assert np.abs(y[:, :, ::st, ::st] - g['output']).max() < TOL
     assert abs(float(y.astype(np.float64).mean()) - float(g['out_mean'])) < 1e-5

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from femasr_amd import synth
-from helpers import cfg_name_of, check_indices_near_tie, load_golden, oracle_net, probe_err, synth_weights
+from helpers import assert_golden_probes, cfg_name_of, check_indices_near_tie, load_golden, oracle_net, synth_weights
 
 TOL = 1e-3
 
@@ -31,10 +31,7 @@ def test_full_size_units_match_reference(name):
     assert abs(float(y.astype(np.float64).mean()) - float(g['out_mean'])) < 1e-5
     nbad, _ = check_indices_near_tie(idx, g)
     assert nbad == 0
-    for k, v in net.probes.items():
-        if 'probe_pos_' + k in g:
-            err, scale = probe_err(g, k, v)
-            assert err <= 2e-5 * max(scale, 1.0), (k, err, scale)
+    assert_golden_probes(g, net.probes, name)
 
 
 def test_tiled_testset_image_first_tile_matches_reference():
