@@ -42,7 +42,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 103      # femasr_version(): FEMASR_ACT_RELU, the femasr_lpips_* entry points (femasr_conv_args ends with w_bf16s)
+ABI_VERSION = 104      # femasr_version(): the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -124,6 +124,9 @@ SIGNATURES = {
     'femasr_lpips_tap_partials': (c_int, [c_int, c_int]),
     'femasr_lpips_tap': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, c_int, vp, vp]),
     'femasr_lpips_finalize': (c_int, [vp, vp, c_int, c_int, ctypes.POINTER(ctypes.c_int32), vp, vp]),
+    'femasr_psnr_ssim_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_psnr_ssim': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, szt]),
+    'femasr_ssim_window': (c_int, [ctypes.POINTER(ctypes.c_double)]),
     'femasr_clock_probe': (c_int, [vp, c_int, vp]),
     'femasr_clock_probe_entries': (c_int, []),
 }

@@ -13,7 +13,9 @@ What is mirrored (same names, argument meaning and behaviour):
   extract_gt_indices       femasr_model.py:144-146  `net_hq(gt)` -> indices
 What is NOT here: training (optimizers, losses, discriminator, schedulers), best-model bookkeeping, tensorboard.
 Metrics: the reference evaluates them with `pyiqa` (not installed here): 'psnr' and 'ssim' follow the BasicSR
-definitions (crop_border, test_y_channel on the BT.601 Y of the uint8-rounded image); 'lpips' (AlexNet) and 'lpips-vgg'
+definitions (crop_border, test_y_channel on the BT.601 Y of the uint8-rounded image).  calculate_psnr / calculate_ssim below
+(numpy / scipy, fp64) ARE those definitions; validation scores them on the GPU (femasr_amd.psnr_ssim, csrc/psnr_ssim.hip) on the
+uint8 SR and GT images already on the device, within 1e-9 dB / 1e-12 of these functions.  'lpips' (AlexNet) and 'lpips-vgg'
 (VGG16) are LPIPS v0.1 on the GPU (femasr_amd.lpips, csrc/lpips.hip) when their options carry `pretrained_model_path`
 (pyiqa's keyword; optionally `backbone_model_path`): scored on (sr_u8 / 255, gt) as femasr_model.py:262 does, the uint8 SR
 image never leaving the device.  Without a weight file (weights are never downloaded) they, like every other type (niqe,
@@ -29,6 +31,7 @@ import torch
 
 from .. import imgproc
 from .. import lpips as lpips_metric
+from .. import psnr_ssim
 from ..archs import build_network
 from . import MODEL_REGISTRY
 
@@ -171,6 +174,9 @@ class FeMaSRModel:
         self.metric_results = {name: 0.0 for name in metrics}
         gpu_metrics = {name: self._gpu_metric(name, m) for name, m in metrics.items()
                        if m.get('type') in lpips_metric.METRIC_NETS and m.get('pretrained_model_path')}
+        # psnr / ssim on the device; the CPU functions in _METRICS are their definition
+        pixel_metrics = {name: psnr_ssim.create_metric(m['type'], **{k: v for k, v in m.items() if k not in ('type', 'better')})
+                         for name, m in metrics.items() if m.get('type') in _METRICS}
         skipped = sorted(name for name, m in metrics.items() if m.get('type') not in _METRICS and name not in gpu_metrics)
         if skipped:
             logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), '
@@ -180,10 +186,10 @@ class FeMaSRModel:
             img_name = os.path.splitext(os.path.basename(val_data['lq_path'][0]))[0]
             self.feed_data(val_data)
             self.test()
-            # tensor2img (img_util.py:38-94) on the GPU: clamp / x255 / round-half-even in a HIP kernel, uint8 crosses PCIe
+            # tensor2img (img_util.py:38-94) on the GPU: clamp / x255 / round-half-even in a HIP kernel; uint8 crosses PCIe only to be saved
             sr_u8 = imgproc.output_to_u8(self.output)
-            sr_img = sr_u8.cpu().numpy()
             if save_img:
+                sr_img = sr_u8.cpu().numpy()
                 suffix = val_opt.get('suffix') or self.opt['name']
                 save_img_path = os.path.join(self.opt['path']['visualization'], dataset_name, f'{img_name}_{suffix}.png')
                 os.makedirs(os.path.dirname(save_img_path), exist_ok=True)
@@ -192,11 +198,9 @@ class FeMaSRModel:
                     os.makedirs(save_as_dir, exist_ok=True)
                     Image.fromarray(sr_img, 'RGB').save(os.path.join(save_as_dir, f'{img_name}.png'))
             if metrics and hasattr(self, 'gt'):
-                gt_img = imgproc.output_to_u8(self.gt).cpu().numpy()
-                for name, m in metrics.items():
-                    fn = _METRICS.get(m.get('type'))
-                    if fn is not None:
-                        self.metric_results[name] += fn(sr_img, gt_img, **{k: v for k, v in m.items() if k not in ('type', 'better')})
+                gt_u8 = imgproc.output_to_u8(self.gt)
+                for name, fn in pixel_metrics.items():
+                    self.metric_results[name] += fn(sr_u8, gt_u8)
                 if gpu_metrics:
                     # metric_data = [img2tensor(sr_img).unsqueeze(0) / 255, self.gt] (femasr_model.py:262), the /255 in a HIP kernel
                     sr = imgproc.u8_to_input(sr_u8)

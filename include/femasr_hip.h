@@ -59,7 +59,7 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -366,6 +366,26 @@ int femasr_lpips_tap_partials(int H, int W);
 int femasr_lpips_tap(void *stream, const float *f, int B2, int H, int W, int C, const float *w_lin, int pool, float *pooled_out,
                      double *partials);
 int femasr_lpips_finalize(void *stream, const double *partials, int B, int ntaps, const int32_t *tap_hw, float *out, float *per_layer);
+
+/* ---- PSNR / SSIM: validation's 'psnr' / 'ssim' metrics (femasr_model.py:29-34,259-262; calculate_psnr_ssim.py) ----
+ * a, b: B pairs of (H,W,3) uint8 RGB HWC images, (B,H,W,3) back to back.  crop_border c scores [c:H-c, c:W-c]; test_y = 1 scores the fp64
+ * BT.601 luma Y = (x/255) . [65.481, 128.553, 24.966] + 16 (not rounded), test_y = 0 the three channels as fp64.  Per pair, fp64 on the
+ * device (each output may be NULL, not all three):
+ *   mse_out[B]   mean of (a - b)² over the cropped pixels (and channels); in RGB mode numpy's value bit for bit (integer terms, exact sum)
+ *   psnr_out[B]  10 log10(255² / mse), +inf where mse == 0
+ *   ssim_out[B]  mean of the SSIM map over the (H-2c-10) x (W-2c-10) valid positions of an 11x11 Gaussian window (sigma 1.5), C1 = (0.01*255)²,
+ *                C2 = (0.03*255)²; RGB: the three channel SSIMs averaged in channel order.  The window sums are scipy.signal.convolve2d's
+ *                (same products, same order), so on the same plane the map is _ssim_plane's bit for bit (in RGB mode always; Y may
+ *                differ from numpy's by 1 ulp where a BLAS sums the dot product in another order).
+ * The definitions are calculate_psnr / calculate_ssim in femasr_amd/models/femasr_model.py.  Two launches (the two metrics' partials in one,
+ * a fixed-order per-pair finalize), no atomics, no host synchronisation, nothing allocated: deterministic and batch-invariant.
+ * Refused with FEMASR_ERR_INVALID before any launch: B < 1, B > 65535, test_y not 0 / 1, crop_border < 0, 2 crop_border >= H or >= W,
+ * B H W 3 >= 2^31 and, when ssim_out is set, a cropped size below 11x11.  workspace_bytes sizes for any of the outputs (it cannot refuse
+ * the last case); `ws` >= that size, 256-byte aligned.  femasr_ssim_window writes the 121 window weights (row-major, a HOST array). */
+int femasr_psnr_ssim_workspace_bytes(int B, int H, int W, int crop_border, int test_y, size_t *bytes);
+int femasr_psnr_ssim(void *stream, const uint8_t *a, const uint8_t *b, int B, int H, int W, int crop_border, int test_y, double *psnr_out,
+                     double *ssim_out, double *mse_out, void *ws, size_t ws_bytes);
+int femasr_ssim_window(double *win);
 
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
