@@ -14,7 +14,10 @@ anything on the path — every forward goes through the C ABI
 GPU is missing (no CPU / eager fallback).
 """
 import ctypes
+import functools
+import inspect
 import math
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -99,6 +102,33 @@ def _rstb(dim=256, depth=6, heads=8, ws=8):             # network_swinir.py:419-
 
 def _up_block(cin, cout):   # Upsample, Conv, ResBlock, ResBlock  (femasr_arch.py:171-176, 201-206)
     return _seq(None, nn.Conv2d(cin, cout, 3, 1, 1), _resblock(cout), _resblock(cout))
+
+
+# --------------------------------------------------------------------------- tile formats
+class _TileFormat(NamedTuple):
+    """Everything that differs between the two image formats the tiled path runs in; the schedule (`FeMaSRNet._tiled`), the
+    extract / paste helpers and the native forward call are written once against it.  Tensor shapes: tiling.tile_shape(dtype, ...)."""
+    dtype: torch.dtype
+    bchw: Callable          # tensor -> (batch, channel, height, width)
+    window: Callable        # (tensor, y0, y1, x0, x1) -> the view [y0:y1, x0:x1] of every image (host tensors)
+    native_bc: Callable     # (batch, channel) -> how the native tile calls take them (the uint8 kernels are RGB only)
+    extract: str            # native symbols
+    paste: str
+    forward: str
+
+
+_FP32 = _TileFormat(torch.float32, lambda t: tuple(t.shape), lambda t, y0, y1, x0, x1: t[:, :, y0:y1, x0:x1], lambda b, c: (b, c),
+                    'femasr_extract_tiles', 'femasr_paste_tiles', 'femasr_forward')                 # (B, C, H, W): test / test_tile
+_U8 = _TileFormat(torch.uint8, lambda t: (t.shape[0], t.shape[3], t.shape[1], t.shape[2]), lambda t, y0, y1, x0, x1: t[:, y0:y1, x0:x1, :],
+                  lambda b, c: (b,), 'femasr_extract_tiles_u8', 'femasr_paste_tiles_u8', 'femasr_forward_u8')   # (B, H, W, 3): test_u8 / test_tile_u8
+
+
+def _takes_out(fn):
+    """False when `fn` (`test` / `test_u8`, possibly replaced by a stand-in: the CPU-side tests of the host logic) has no `out=`."""
+    try:
+        return 'out' in inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
 
 
 # --------------------------------------------------------------------------- the arch
@@ -308,11 +338,18 @@ class FeMaSRNet(nn.Module):
         except Exception:
             pass
 
-    def _workspace(self, nbytes, device):
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
+    def _workspace(self, query, h, dims, device):
+        """The scratch tensor of the native calls, at least as large as `query(h, *dims, &bytes)` asks for (grown, never shrunk)."""
+        nbytes = ctypes.c_size_t()
+        _lib.check(query(h, *dims, ctypes.byref(nbytes)))
+        if self._ws is None or self._ws.numel() < nbytes.value or self._ws.device != device:
             self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+            self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
         return self._ws
+
+    @staticmethod
+    def _stream(device):
+        return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
     def enable_profile(self, on=True):
         lib, h = self._native(next(self.parameters()).device)
@@ -331,21 +368,27 @@ class FeMaSRNet(nn.Module):
         return out
 
     # ------------------------------------------------------------------ the path
-    def _launch(self, lib, h, x, pad_mode, oh, ow, sizes, out=None):
-        b, _, hh, ww = x.shape
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.femasr_workspace_bytes(h, b, hh, ww, pad_mode, ctypes.byref(nbytes)))
-        ws = self._workspace(nbytes.value, x.device)
+    def _forward_native(self, lib, h, fmt, x, pad_mode, out=None, flags=(), indices=True):
+        """One `femasr_forward` / `femasr_forward_u8` (the format's) on the current stream: output geometry, workspace and result
+        tensor (`out`, when given, is validated and written in place).  `flags`: the native arguments in front of `pad_mode`
+        (`femasr_forward_u8`'s bgr).  Returns (out, all VQ indices as one flat tensor or None, workspace, [(qh, qw)] per codebook)."""
+        b, _, hh, ww = fmt.bchw(x)
+        oh, ow, nq = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        qh, qw = (ctypes.c_int * _lib.MAX_CODEBOOKS)(), (ctypes.c_int * _lib.MAX_CODEBOOKS)()
+        _lib.check(lib.femasr_forward_shapes(h, hh, ww, pad_mode, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(nq),
+                                             ctypes.byref(qh), ctypes.byref(qw)))
+        qhw = [(qh[k], qw[k]) for k in range(nq.value)]
+        ws = self._workspace(lib.femasr_workspace_bytes, h, (b, hh, ww, pad_mode), x.device)
+        shape = tiling.tile_shape(fmt.dtype, b, 3, oh.value, ow.value)
         if out is None:
-            out = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=x.device)
-        elif (tuple(out.shape) != (b, 3, oh, ow) or out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous()):
-            raise ValueError(f'out= must be a contiguous float32 tensor of shape {(b, 3, oh, ow)} on {x.device}, got '
+            out = torch.empty(shape, dtype=fmt.dtype, device=x.device)
+        elif tuple(out.shape) != shape or out.dtype != fmt.dtype or out.device != x.device or not out.is_contiguous():
+            raise ValueError(f'out= must be a contiguous {fmt.dtype} tensor of shape {shape} on {x.device}, got '
                              f'{tuple(out.shape)} {out.dtype} on {out.device}')
-        idx_all = torch.empty((sum(sizes),), dtype=torch.int64, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.femasr_forward(h, ctypes.c_void_p(stream), _lib.ptr(x), b, hh, ww, pad_mode,
-                                      _lib.ptr(out), _lib.ptr(idx_all), _lib.ptr(ws), ws.numel()))
-        return out, idx_all, ws
+        idx_all = torch.empty((sum(b * a * c for a, c in qhw),), dtype=torch.int64, device=x.device) if indices else None
+        _lib.check(getattr(lib, fmt.forward)(h, self._stream(x.device), _lib.ptr(x), b, hh, ww, *flags, pad_mode, _lib.ptr(out),
+                                             None if idx_all is None else _lib.ptr(idx_all), _lib.ptr(ws), ws.numel()))
+        return out, idx_all, ws, qhw
 
     def _run(self, x, pad_mode, out=None):
         if x.dim() != 4 or x.shape[1] != self.in_channel:
@@ -353,11 +396,6 @@ class FeMaSRNet(nn.Module):
         lib, h = self._native(x.device)
         x = x.detach().to(torch.float32).contiguous()
         b, _, hh, ww = x.shape
-        oh, ow, nq = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        qh, qw = (ctypes.c_int * _lib.MAX_CODEBOOKS)(), (ctypes.c_int * _lib.MAX_CODEBOOKS)()
-        _lib.check(lib.femasr_forward_shapes(h, hh, ww, pad_mode, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(nq),
-                                             ctypes.byref(qh), ctypes.byref(qw)))
-        sizes = [b * qh[k] * qw[k] for k in range(nq.value)]
         if self.use_graph:
             key = (b, hh, ww, pad_mode, self.num_streams, self.decoder_math, self.linear_math, x.device.index)
             ent = self._graphs.get(key)
@@ -365,24 +403,24 @@ class FeMaSRNet(nn.Module):
                 if len(self._graphs) > 8:
                     self._graphs.clear()
                 xs = x.clone()
-                self._launch(lib, h, xs, pad_mode, oh.value, ow.value, sizes)        # warm-up: lazy one-time setup outside capture
+                self._forward_native(lib, h, _FP32, xs, pad_mode)                    # warm-up: lazy one-time setup outside capture
                 torch.cuda.synchronize(x.device)
                 g = torch.cuda.CUDAGraph()
                 self._ws = None                                                      # the graph owns its workspace
                 with torch.cuda.graph(g):
-                    so, si, sw = self._launch(lib, h, xs, pad_mode, oh.value, ow.value, sizes)
+                    so, si, sw, qhw = self._forward_native(lib, h, _FP32, xs, pad_mode)
                 self._ws = None
-                ent = self._graphs[key] = (g, xs, so, si, sw)
-            g, xs, so, si, _ = ent
+                ent = self._graphs[key] = (g, xs, so, si, sw, qhw)
+            g, xs, so, si, _, qhw = ent
             xs.copy_(x)
             g.replay()
             out, idx_all = (so.clone() if out is None else out.copy_(so)), si.clone()
         else:
-            out, idx_all, _ = self._launch(lib, h, x, pad_mode, oh.value, ow.value, sizes, out)
+            out, idx_all, _, qhw = self._forward_native(lib, h, _FP32, x, pad_mode, out)
         idx, off = [], 0
-        for k in range(nq.value):
-            idx.append(idx_all[off:off + sizes[k]].view(b, 1, qh[k], qw[k]))
-            off += sizes[k]
+        for qh, qw in qhw:
+            idx.append(idx_all[off:off + b * qh * qw].view(b, 1, qh, qw))
+            off += b * qh * qw
         return out, idx
 
     @torch.no_grad()
@@ -394,27 +432,19 @@ class FeMaSRNet(nn.Module):
         kernel stores into (the tiled / multi-GPU callers pass slices of their result or all-gather send buffers)."""
         if img_u8.device.type != 'cuda':
             raise _lib.FemasrError('test_u8: tensor must be on the GPU (no CPU fallback)')
+        x, single = self._u8_batch(img_u8)
+        lib, h = self._native(x.device)
+        out = self._forward_native(lib, h, _U8, x, 1, out, flags=(int(bool(bgr)),), indices=False)[0]
+        return out[0] if single else out
+
+    @staticmethod
+    def _u8_batch(img_u8):
+        """uint8 (H,W,3) or (B,H,W,3) -> (contiguous (B,H,W,3), whether the caller's image had no batch axis)."""
         single = img_u8.dim() == 3
         x = img_u8.unsqueeze(0) if single else img_u8
         if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
             raise ValueError(f'expected uint8 (H,W,3) or (B,H,W,3), got {img_u8.dtype} {tuple(img_u8.shape)}')
-        lib, h = self._native(x.device)
-        x = x.contiguous()
-        b, hh, ww, _ = x.shape
-        oh, ow, nq = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        qh, qw = (ctypes.c_int * _lib.MAX_CODEBOOKS)(), (ctypes.c_int * _lib.MAX_CODEBOOKS)()
-        _lib.check(lib.femasr_forward_shapes(h, hh, ww, 1, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(nq), ctypes.byref(qh), ctypes.byref(qw)))
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.femasr_workspace_bytes(h, b, hh, ww, 1, ctypes.byref(nbytes)))
-        ws = self._workspace(nbytes.value, x.device)
-        if out is None:
-            out = torch.empty((b, oh.value, ow.value, 3), dtype=torch.uint8, device=x.device)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (b, oh.value, ow.value, 3) or not out.is_contiguous() or out.device != x.device):
-            raise ValueError(f'test_u8(out=...): expected a contiguous uint8 {(b, oh.value, ow.value, 3)} tensor on {x.device}')
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lib.femasr_forward_u8(h, ctypes.c_void_p(stream), _lib.ptr(x), b, hh, ww, int(bool(bgr)), 1, _lib.ptr(out), None,
-                                         _lib.ptr(ws), ws.numel()))
-        return out[0] if single else out
+        return x.contiguous(), single
 
     @torch.no_grad()
     def encode_and_decode(self, input, gt_indices=None, current_iter=None):
@@ -458,14 +488,10 @@ class FeMaSRNet(nn.Module):
         lib, h = self._native(dev)
         idx = indices.to(device=dev, dtype=torch.int64).contiguous()
         b, _, qh, qw = idx.shape
-        nbytes = ctypes.c_size_t()
-        _lib.check(lib.femasr_decode_workspace_bytes(h, b, qh, qw, ctypes.byref(nbytes)))
-        ws = self._workspace(nbytes.value, dev)
+        ws = self._workspace(lib.femasr_decode_workspace_bytes, h, (b, qh, qw), dev)
         up = 2 ** self.max_depth
         out = torch.empty((b, 3, qh * up, qw * up), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.femasr_decode_indices(h, ctypes.c_void_p(stream), _lib.ptr(idx), b, qh, qw, _lib.ptr(out),
-                                             _lib.ptr(ws), ws.numel()))
+        _lib.check(lib.femasr_decode_indices(h, self._stream(dev), _lib.ptr(idx), b, qh, qw, _lib.ptr(out), _lib.ptr(ws), ws.numel()))
         return out
 
     # ------------------------------------------------------------------ tiled inference
@@ -477,33 +503,49 @@ class FeMaSRNet(nn.Module):
         supplies the collective (femasr_amd.distributed.TileExchange: ONE RCCL all-gather on persistent buffers the tiles were
         written into).  paste=False (ranks other than the one that needs the image): take part in the collective, skip the
         canvas (returns None)."""
-        batch, channel, height, width = input.shape
+        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste)
+
+    @torch.no_grad()
+    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False):
+        """`test_tile` on uint8 images end to end (round 6; the CLI's tiled branch, inference_femasr.py:58-67 with femasr_arch.py:387-447):
+        uint8 (H,W,3) / (B,H,W,3) in -> uint8 (sH,sW,3) / (B,sH,sW,3) out.  Tiles are cropped as uint8, every batched call is ONE
+        `test_u8` (decode fused into the mirror-pad kernel, tensor2img into the crop kernel, which stores straight into the result /
+        all-gather send buffer), the all-gather and the paste move one byte per value (a quarter of the fp32 path's xGMI and canvas
+        traffic; no 805-MB fp32 canvas at 8192^2).  Bit-identical to output_to_u8(test_tile(u8_to_input(img))): tensor2img is
+        element-wise and every output pixel comes from exactly one tile."""
+        x, single = self._u8_batch(img_u8)
+        output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste)
+        return output[0] if single and output is not None else output
+
+    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste):
+        """The tile schedule of `test_tile` and `test_tile_u8`: `x` is the contiguous image batch in tile format `fmt`,
+        `run(crops[, out=])` the batched call on the crops of one shape class.  Returns the canvas (None with paste=False)."""
+        batch, channel, height, width = fmt.bchw(x)
         s = self.scale_factor
-        tiles = tiling.enumerate_tiles(height, width, tile_size, tile_pad)
-        classes = tiling.shape_classes(tiles)
+        classes = tiling.shape_classes(tiling.enumerate_tiles(height, width, tile_size, tile_pad))
         owned_all = tiling.assign(classes, world_size, s)          # (once per call: every rank's share - the paste below indexes it; ADVICE r5)
         mine = owned_all[rank]
         # `time_split = True`: record where the call's time goes (events on the current stream; read back in `last_split_ms`
         # = {'compute', 'gather', 'paste', 'tiles_owned'} after a synchronize) - bench.py --workload tile2048 reports it per rank
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if (getattr(self, 'time_split', False) and input.is_cuda) else None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if (getattr(self, 'time_split', False) and x.is_cuda) else None
         if ev:
             ev[0].record()
-        # One result buffer per shape class, written in place by the batched test() calls (`out=`).  With a gather object that owns
+        # One result buffer per shape class, written in place by the batched calls (`out=`).  With a gather object that owns
         # persistent send buffers (femasr_amd.distributed.TileExchange.send_views) the buffers ARE this rank's all-gather send slab.
         alloc = getattr(gather, 'send_views', None) if world_size > 1 else None
         if alloc is not None:
-            results = alloc(classes, batch, channel, s, torch.float32, input.device)
+            results = alloc(classes, batch, channel, s, fmt.dtype, x.device)
         else:
-            results = {hw: torch.empty((len(tl) * batch, channel, hw[0] * s, hw[1] * s), dtype=torch.float32, device=input.device)
-                       for hw, tl in mine.items()}
+            results = {hw: torch.empty(tiling.tile_shape(fmt.dtype, len(tl) * batch, channel, hw[0] * s, hw[1] * s), dtype=fmt.dtype,
+                                       device=x.device) for hw, tl in mine.items()}
         per_call = max(1, self.max_tile_batch // batch)
-        in_place = self._test_takes_out()
+        in_place = _takes_out(run)
         for hw, tl in mine.items():
             for i in range(0, len(tl), per_call):
                 chunk = tl[i:i + per_call]
                 dst = results[hw][i * batch:(i + len(chunk)) * batch]
-                crops = self._extract_tiles(input, chunk, hw)
-                y = self.test(crops, out=dst) if in_place else self.test(crops)
+                crops = self._extract_tiles(fmt, x, chunk, hw)
+                y = run(crops, out=dst) if in_place else run(crops)
                 if y.data_ptr() != dst.data_ptr():
                     dst.copy_(y)
         if ev:
@@ -516,126 +558,22 @@ class FeMaSRNet(nn.Module):
             per_rank = [results]
         if ev:
             ev[2].record()
-        if not paste:
-            if ev:
-                ev[3].record()
-                self._split_events = (ev, sum(len(tl) for tl in mine.values()))
-            return None
-        output = input.new_zeros((batch, channel, height * s, width * s))
-        for r, res in enumerate(per_rank):
-            for hw, tl in owned_all[r].items():
-                if tl:
-                    self._paste_tiles(output, res[hw], tl, batch, s)
+        output = None
+        if paste:
+            output = x.new_zeros(tiling.tile_shape(fmt.dtype, batch, channel, height * s, width * s))
+            for r, res in enumerate(per_rank):
+                for hw, tl in owned_all[r].items():
+                    if tl:
+                        self._paste_tiles(fmt, output, res[hw], tl, batch, s)
         if ev:
             ev[3].record()
             self._split_events = (ev, sum(len(tl) for tl in mine.values()))
         return output
 
-    @torch.no_grad()
-    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False):
-        """`test_tile` on uint8 images end to end (round 6; the CLI's tiled branch, inference_femasr.py:58-67 with femasr_arch.py:387-447):
-        uint8 (H,W,3) / (B,H,W,3) in -> uint8 (sH,sW,3) / (B,sH,sW,3) out.  Tiles are cropped as uint8, every batched call is ONE
-        `test_u8` (decode fused into the mirror-pad kernel, tensor2img into the crop kernel, which stores straight into the result /
-        all-gather send buffer), the all-gather and the paste move one byte per value (a quarter of the fp32 path's xGMI and canvas
-        traffic; no 805-MB fp32 canvas at 8192^2).  Bit-identical to output_to_u8(test_tile(u8_to_input(img))): tensor2img is
-        element-wise and every output pixel comes from exactly one tile."""
-        single = img_u8.dim() == 3
-        x = img_u8.unsqueeze(0) if single else img_u8
-        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-            raise ValueError(f'expected uint8 (H,W,3) or (B,H,W,3), got {img_u8.dtype} {tuple(img_u8.shape)}')
-        x = x.contiguous()
-        batch, height, width, channel = x.shape
-        s = self.scale_factor
-        tiles = tiling.enumerate_tiles(height, width, tile_size, tile_pad)
-        classes = tiling.shape_classes(tiles)
-        owned_all = tiling.assign(classes, world_size, s)          # (once: every rank's share, for the paste below)
-        mine = owned_all[rank]
-        alloc = getattr(gather, 'send_views', None) if world_size > 1 else None
-        if alloc is not None:
-            results = alloc(classes, batch, channel, s, torch.uint8, x.device, layout='nhwc')
-        else:
-            results = {hw: torch.empty((len(tl) * batch, hw[0] * s, hw[1] * s, channel), dtype=torch.uint8, device=x.device)
-                       for hw, tl in mine.items()}
-        per_call = max(1, self.max_tile_batch // batch)
-        in_place = 'out' in self._signature_of(self.test_u8)
-        for hw, tl in mine.items():
-            for i in range(0, len(tl), per_call):
-                chunk = tl[i:i + per_call]
-                dst = results[hw][i * batch:(i + len(chunk)) * batch]
-                crops = self._extract_tiles_u8(x, chunk, hw)
-                y = self.test_u8(crops, bgr=bgr, out=dst) if in_place else self.test_u8(crops, bgr=bgr)
-                if y.data_ptr() != dst.data_ptr():
-                    dst.copy_(y)
-        if world_size > 1:
-            if gather is None:
-                raise ValueError('world_size > 1 needs a gather callable')
-            per_rank = gather(results, classes, batch, channel, s, layout='nhwc')
-        else:
-            per_rank = [results]
-        if not paste:
-            return None
-        output = x.new_zeros((batch, height * s, width * s, channel))
-        for r, res in enumerate(per_rank):
-            for hw, tl in owned_all[r].items():
-                if tl:
-                    self._paste_tiles_u8(output, res[hw], tl, batch, s)
-        return output[0] if single else output
-
-    @staticmethod
-    def _signature_of(fn):
-        import inspect
-        try:
-            return inspect.signature(fn).parameters
-        except (TypeError, ValueError):
-            return {}
-
-    @staticmethod
-    def _extract_tiles_u8(x, chunk, hw):
-        """uint8 crops `img[:, y0p:y1p, x0p:x1p, :]` of one shape class as one (n*B, th, tw, 3) batch (tile-major): one native launch
-        (host tensors: slicing, for the CPU-side tests of the partition / gather logic)."""
-        if not x.is_cuda:
-            return torch.cat([x[:, t.y0p:t.y1p, t.x0p:t.x1p, :] for t in chunk], 0).contiguous()
-        lib = _lib.load()
-        b, h, w, _ = x.shape
-        yx = torch.tensor([v for t in chunk for v in (t.y0p, t.x0p)], dtype=torch.int32).to(x.device, non_blocking=True)
-        out = torch.empty((len(chunk) * b, hw[0], hw[1], 3), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.femasr_extract_tiles_u8(torch.cuda.current_stream().cuda_stream, x.data_ptr(), b, h, w, yx.data_ptr(),
-                                                   len(chunk), hw[0], hw[1], out.data_ptr()))
-        return out
-
-    @staticmethod
-    def _paste_tiles_u8(output, block, tl, batch, s):
-        if not output.is_cuda:
-            for k, t in enumerate(tl):
-                ys, ye, xs, xe = t.out_src(s)
-                dy0, dy1, dx0, dx1 = t.out_dst(s)
-                output[:, dy0:dy1, dx0:dx1, :] = block[k * batch:(k + 1) * batch, ys:ye, xs:xe, :]
-            return
-        lib = _lib.load()
-        block = block.contiguous()
-        rects, hmax = [], 0
-        for t in tl:
-            ys, ye, xs, xe = t.out_src(s)
-            dy0, _, dx0, _ = t.out_dst(s)
-            rects += [ys, xs, dy0, dx0, ye - ys, xe - xs]
-            hmax = max(hmax, ye - ys)
-        rd = torch.tensor(rects, dtype=torch.int32).to(output.device, non_blocking=True)
-        with torch.cuda.device(output.device):
-            _lib.check(lib.femasr_paste_tiles_u8(torch.cuda.current_stream().cuda_stream, block.data_ptr(), batch, len(tl), block.shape[1],
-                                                 block.shape[2], rd.data_ptr(), hmax, output.shape[1], output.shape[2], output.data_ptr()))
-
-    def _test_takes_out(self):
-        """False when `test` was replaced by a stand-in without the `out=` parameter (CPU-side tests of the host logic)."""
-        import inspect
-        try:
-            return 'out' in inspect.signature(self.test).parameters
-        except (TypeError, ValueError):
-            return False
-
     @property
     def last_split_ms(self):
-        """{'compute', 'gather', 'paste'} milliseconds of the last `test_tile` call made with `time_split = True` (synchronises)."""
+        """{'compute', 'gather', 'paste'} milliseconds of the last `test_tile` / `test_tile_u8` call made with `time_split = True`
+        (synchronises)."""
         rec = getattr(self, '_split_events', None)
         if rec is None:
             return None
@@ -645,33 +583,28 @@ class FeMaSRNet(nn.Module):
                 'paste': round(ev[2].elapsed_time(ev[3]), 3), 'tiles_owned': owned}
 
     @staticmethod
-    def _extract_tiles(input, chunk, hw):
-        """torch.cat of the reference's crops `input[:, :, y0p:y1p, x0p:x1p]` (femasr_arch.py:412-426) for the tiles of one
-        shape class: one femasr_extract_tiles launch on the GPU (host tensors: plain slicing, used by the CPU-side tests of
-        the partition / gather logic only)."""
-        if not input.is_cuda:
-            return torch.cat([input[:, :, t.y0p:t.y1p, t.x0p:t.x1p] for t in chunk], 0)
-        lib = _lib.load()
-        b, c, h, w = input.shape
-        x = input.contiguous().float()
+    def _extract_tiles(fmt, x, chunk, hw):
+        """torch.cat of the reference's crops `input[:, :, y0p:y1p, x0p:x1p]` (femasr_arch.py:412-426; uint8: `img[:, y0p:y1p,
+        x0p:x1p, :]`) for the tiles of one shape class, tile-major: one launch of the format's extract kernel on the GPU (host
+        tensors: plain slicing, used by the CPU-side tests of the partition / gather logic only)."""
+        if not x.is_cuda:
+            return torch.cat([fmt.window(x, t.y0p, t.y1p, t.x0p, t.x1p) for t in chunk], 0)
+        b, c, h, w = fmt.bchw(x)
         yx = torch.tensor([v for t in chunk for v in (t.y0p, t.x0p)], dtype=torch.int32).to(x.device, non_blocking=True)
-        out = torch.empty((len(chunk) * b, c, hw[0], hw[1]), dtype=torch.float32, device=x.device)
+        out = torch.empty(tiling.tile_shape(fmt.dtype, len(chunk) * b, c, hw[0], hw[1]), dtype=fmt.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.femasr_extract_tiles(torch.cuda.current_stream().cuda_stream, x.data_ptr(), b, c, h, w, yx.data_ptr(),
-                                                len(chunk), hw[0], hw[1], out.data_ptr()))
+            _lib.check(getattr(_lib.load(), fmt.extract)(torch.cuda.current_stream().cuda_stream, x.data_ptr(), *fmt.native_bc(b, c), h, w,
+                                                         yx.data_ptr(), len(chunk), hw[0], hw[1], out.data_ptr()))
         return out
 
     @staticmethod
-    def _paste_tiles(output, block, tl, batch, s):
+    def _paste_tiles(fmt, output, block, tl, batch, s):
         """`output[:, :, dst] = output_tile[:, :, src]` (femasr_arch.py:443-446) for all tiles of one shape class and rank."""
         if not output.is_cuda:
             for k, t in enumerate(tl):
-                ys, ye, xs, xe = t.out_src(s)
-                dy0, dy1, dx0, dx1 = t.out_dst(s)
-                output[:, :, dy0:dy1, dx0:dx1] = block[k * batch:(k + 1) * batch, :, ys:ye, xs:xe]
+                fmt.window(output, *t.out_dst(s))[...] = fmt.window(block[k * batch:(k + 1) * batch], *t.out_src(s))
             return
-        lib = _lib.load()
-        block = block.contiguous().float()
+        block = block.contiguous().to(fmt.dtype)
         rects, hmax = [], 0
         for t in tl:
             ys, ye, xs, xe = t.out_src(s)
@@ -679,7 +612,8 @@ class FeMaSRNet(nn.Module):
             rects += [ys, xs, dy0, dx0, ye - ys, xe - xs]
             hmax = max(hmax, ye - ys)
         rd = torch.tensor(rects, dtype=torch.int32).to(output.device, non_blocking=True)
+        _, c, th, tw = fmt.bchw(block)
+        _, _, oh, ow = fmt.bchw(output)
         with torch.cuda.device(output.device):
-            _lib.check(lib.femasr_paste_tiles(torch.cuda.current_stream().cuda_stream, block.data_ptr(), batch, output.shape[1], len(tl),
-                                              block.shape[2], block.shape[3], rd.data_ptr(), hmax, output.shape[2], output.shape[3],
-                                              output.data_ptr()))
+            _lib.check(getattr(_lib.load(), fmt.paste)(torch.cuda.current_stream().cuda_stream, block.data_ptr(), *fmt.native_bc(batch, c),
+                                                       len(tl), th, tw, rd.data_ptr(), hmax, oh, ow, output.data_ptr()))

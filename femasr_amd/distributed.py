@@ -55,9 +55,8 @@ class TileGather:
     Sizes follow from the deterministic partition (tiling.partition), so no size exchange is needed; every
     rank's slab is `cap` = the largest rank payload (ranks with fewer tiles leave their tail unused)."""
 
-    def __init__(self, classes, batch, channel, scale, dtype, device, group=None, layout='nchw'):
+    def __init__(self, classes, batch, channel, scale, dtype, device, group=None):
         self.group = group
-        self.layout = layout            # 'nchw': fp32 tiles (n, C, H, W) of test_tile; 'nhwc': uint8 tiles (n, H, W, C) of test_tile_u8
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         self.classes, self.batch, self.channel, self.scale = classes, batch, channel, scale
@@ -71,9 +70,8 @@ class TileGather:
         d, off = {}, 0
         for hw, tl in self.owned[r].items():
             n = _class_numel(hw, len(tl), self.batch, self.channel, self.scale)
-            shp = (len(tl) * self.batch, self.channel, hw[0] * self.scale, hw[1] * self.scale) if self.layout == 'nchw' else \
-                  (len(tl) * self.batch, hw[0] * self.scale, hw[1] * self.scale, self.channel)
-            d[hw] = flat[off:off + n].view(shp)
+            # (fp32 tiles of test_tile are (n, C, H, W), uint8 tiles of test_tile_u8 (n, H, W, C): the dtype decides)
+            d[hw] = flat[off:off + n].view(tiling.tile_shape(flat.dtype, len(tl) * self.batch, self.channel, hw[0] * self.scale, hw[1] * self.scale))
             off += n
         return d
 
@@ -130,23 +128,23 @@ class TileExchange:
         self._key = None
         self._tg = None
 
-    def _get(self, classes, batch, channel, scale, dtype, device, layout='nchw'):
+    def _get(self, classes, batch, channel, scale, dtype, device):
         # (world size and rank are part of the key: after destroy_process_group + a new init in the same process - or a freed group's
         # id() coming back - a TileGather built for another world would hand stale sizes to the collective)
         key = (tuple((hw, tuple(t.index for t in tl)) for hw, tl in classes.items()), batch, channel, scale, dtype, str(device),
-               dist.get_world_size(self.group), dist.get_rank(self.group), layout)
+               dist.get_world_size(self.group), dist.get_rank(self.group))
         if key != self._key:
             self._tg = None                 # one geometry at a time keeps the footprint bounded
-            self._tg = TileGather(classes, batch, channel, scale, dtype, device, self.group, layout)
+            self._tg = TileGather(classes, batch, channel, scale, dtype, device, self.group)
             self._key = key
         return self._tg
 
-    def send_views(self, classes, batch, channel, scale, dtype, device, layout='nchw'):
-        return self._get(classes, batch, channel, scale, dtype, torch.device(device), layout).send_views()
+    def send_views(self, classes, batch, channel, scale, dtype, device):
+        return self._get(classes, batch, channel, scale, dtype, torch.device(device)).send_views()
 
-    def __call__(self, results, classes, batch, channel, scale, layout='nchw'):
+    def __call__(self, results, classes, batch, channel, scale):
         ref = next(iter(results.values()))
-        tg = self._get(classes, batch, channel, scale, ref.dtype, ref.device, layout)
+        tg = self._get(classes, batch, channel, scale, ref.dtype, ref.device)
         for hw, dst in tg.send_views().items():
             src = results[hw]
             if src.data_ptr() != dst.data_ptr() or src.numel() != dst.numel():
@@ -169,14 +167,14 @@ def _exchange_for(group):
     return _exchanges[sig]
 
 
-def gather_tiles(results, classes, batch, channel, scale, group=None, layout='nchw'):
+def gather_tiles(results, classes, batch, channel, scale, group=None):
     """All-gather every rank's upscaled tiles with ONE `all_gather_into_tensor` on persistent buffers (functional form of
     TileExchange; the tiles are copied into the send slab unless they already live there).
 
-    results: {(h,w): tensor (n_owned*batch, channel, h*s, w*s)} of THIS rank.
+    results: {(h,w): tensor of n_owned*batch tiles, shaped as tiling.tile_shape gives for its dtype} of THIS rank.
     Returns a list (one entry per rank) of dicts with the same structure (views into the receive buffer,
     valid until the next call with the same geometry)."""
-    return _exchange_for(group)(results, classes, batch, channel, scale, layout)
+    return _exchange_for(group)(results, classes, batch, channel, scale)
 
 
 def test_tile_parallel(net, x, tile_size=240, tile_pad=16, group=None, root_only=False):

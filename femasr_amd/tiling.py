@@ -71,6 +71,12 @@ def shape_classes(tiles: List[Tile]) -> "OrderedDict[Tuple[int, int], List[Tile]
     return classes
 
 
+def tile_shape(dtype, n: int, channel: int, h: int, w: int) -> Tuple[int, int, int, int]:
+    """Tensor shape of `n` tiles (and of a canvas): one-byte values are image bytes and keep the CLI's (n, h, w, channel) order
+    (`test_tile_u8`), everything else is network input / output, (n, channel, h, w) (`test_tile`).  `dtype`: a torch dtype."""
+    return (n, h, w, channel) if dtype.itemsize == 1 else (n, channel, h, w)
+
+
 def rank_slice(n: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous block [lo, hi) of n items for `rank`; the first n % world ranks get one extra."""
     q, r = divmod(n, world)
