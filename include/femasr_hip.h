@@ -98,6 +98,11 @@ int femasr_forward_shapes(const femasr_handle *h, int H, int W, int pad_mode, in
 /* Whole hot path: in NCHW fp32 (B,3,H,W) -> out NCHW fp32 (B,3,out_h,out_w) and, if non-NULL, the VQ index maps int64
  * of all codebooks back to back, map q = (B,1,idx_h[q],idx_w[q]).  Replaces FeMaSRNet.encode_and_decode
  * (femasr_arch.py:311-374) inside .test / .forward.  `ws` must be >= femasr_workspace_bytes and 256-byte aligned.
+ * Batch size: the planner gives every conv the fastest form whose offset range holds its tensors (femasr_conv_args, size limits); a
+ * batch whose activations pass 2^31 elements per tensor (x4: more than 101 tiles of 128^2, 25 windows of 272^2 in one call) still
+ * computes every image, on the slower 64-bit forms (256 tiles of 128^2 in one call: the indices of calls of 16, the image within 1e-5 of
+ * theirs; tests/test_gpu_product_anchor.py), so splitting it is faster,
+ * never more correct.  Only B*Ho*Wo >= 2^31 - 256 pixels of one layer is refused (FEMASR_ERR_INVALID, before any launch).
  * Every entry point runs on the handle's device and restores the caller's current device before returning. */
 int femasr_forward(femasr_handle *h, void *stream, const float *in_nchw, int B, int H, int W,
                    int pad_mode, float *out_nchw, int64_t *indices, void *ws, size_t ws_bytes);
@@ -199,6 +204,13 @@ typedef struct {
                              result than the fp32 fmaf chain and bit-identical to oracle/femasr_oracle.c orc_linear_bf16s, which restates
                              the instruction's accumulation arithmetic from hardware probes (kernels_gemm_bf16.hip).  `w` is not read. */
 } femasr_conv_args;
+/* Size limits (each a shape rule evaluated before any launch; DESIGN.md 5.7, tests/test_gpu_product_anchor.py):
+ *   rows B*Ho*Wo < 2^31 - 256 for every form, else FEMASR_ERR_INVALID;
+ *   w_wino: < 2^31 elements per tensor and < 2^27 per image (32-bit byte offsets), else FEMASR_ERR_INVALID;
+ *   w_bf16x3 and the 3x3 form of w_bf16s: B*H*W*Cin < 2^31, else FEMASR_ERR_INVALID;
+ *   the direct form (none of those weights given): the 3x3 stride-1 halo kernels and the Cout = 3 kernel hold the input patch
+ *   offset as a 32-bit ELEMENT offset and are used while B*H*W*Cin < 2^31; a larger input - 2^32 elements and more included - runs
+ *   on the generic implicit GEMM, whose offsets are 64-bit (slower; gn_part is then not accepted).  Nothing wraps silently. */
 int femasr_conv2d(void *stream, const femasr_conv_args *a);
 
 /* GroupNorm(32,eps) moments folded into per-(n,c) scale/shift: y = fmaf(x,a,b) (fema_utils.py:22).

@@ -1,5 +1,6 @@
-"""fp64 restatements of the network's kernel operations, their error bounds, and the inventory of the launches the benchmarked
-workloads make (tests/test_gpu_fp64_anchor.py; CPU self-checks in tests/test_fp64_anchor_host.py).
+"""fp64 restatements of the network's kernel operations, their error bounds, and the inventories of the launches the benchmarked
+workloads make (WORKLOADS, tests/test_gpu_fp64_anchor.py) and of those the CLI and the Python API make by default (PRODUCT_WORKLOADS,
+tests/test_gpu_product_anchor.py); CPU self-checks in tests/test_fp64_anchor_host.py, case runners in tests/anchor_cases.py.
 
 Nothing here reads the oracle: each reference is the plain definition of the operation, evaluated in float64 with torch at sampled
 output positions (the network's inputs are gathered on whichever device holds them).
@@ -52,11 +53,28 @@ def axis_samples(n, tile, extra=(), rng=None, nrand=3):
     return sorted(v for v in s if 0 <= v < n)
 
 
-def conv_positions(B, Ho, Wo, seed, tiles_y=(8, 16), tiles_x=(16,), max_pos=900):
-    """(S, 3) int64 (n, y, x): the structured rows x columns on the first and the last image, random positions on all images."""
+def straddle_images(B, image_bytes, step=2 ** 31):
+    """The images of a (B, ...) tensor of `image_bytes` bytes per image that hold a multiple of `step` bytes (the image a 32-bit
+    byte offset, signed or unsigned, wraps in) and the image after each: sorted indices, empty when the tensor is <= `step` bytes."""
+    s = set()
+    k = step
+    while k < B * image_bytes:
+        n = k // image_bytes                     # byte k is in image n (or is its first byte)
+        s |= {n, min(n + 1, B - 1)}
+        if k % image_bytes == 0 and n > 0:       # the boundary is an image seam: the image that ends there too
+            s.add(n - 1)
+        k += step
+    return sorted(s)
+
+
+def conv_positions(B, Ho, Wo, seed, tiles_y=(8, 16), tiles_x=(16,), max_pos=900, images=()):
+    """(S, 3) int64 (n, y, x): the structured rows x columns on the first and the last image and on every image of `images`
+    (straddle_images: where the offsets of a large tensor wrap; max_pos applies per image), random positions on all images."""
     rng = np.random.default_rng(seed)
     ys, xs = axis_samples(Ho, tiles_y, rng=rng), axis_samples(Wo, tiles_x, rng=rng)
-    grid = [(n, y, x) for n in sorted({0, B - 1}) for y in ys for x in xs]
+    imgs = sorted({0, B - 1} | {int(n) for n in images if 0 <= n < B})
+    grid = [(n, y, x) for n in imgs for y in ys for x in xs]
+    max_pos = max_pos * max(1, (len(imgs) + 1) // 2)
     if len(grid) > max_pos:
         keep = rng.choice(len(grid), max_pos, replace=False)
         border = [i for i, (n, y, x) in enumerate(grid) if y in (0, Ho - 1) or x in (0, Wo - 1)]
@@ -175,6 +193,9 @@ def gn_coeffs_ref(x, gamma, beta, groups=32, eps=1e-6, group_shift=0):
     x NHWC on any device; moments in fp64 on its device.  group_shift: a deliberately wrong channel -> group map (self-checks)."""
     B, H, W, C = x.shape
     cg = C // groups
+    if B > 1 and x.numel() > 2 ** 28:          # large launches: image by image, so the fp64 copies stay one image in size
+        parts = [gn_coeffs_ref(x[n:n + 1], gamma, beta, groups, eps, group_shift) for n in range(B)]
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
     xd = x.to(torch.float64)
     s1 = xd.sum((1, 2))                                          # (B, C)
     s2 = (xd * xd).sum((1, 2))
@@ -264,11 +285,12 @@ def attention_ref(qkv, b, H, W, C, heads, shift, table, windows, ws=8, mask_shif
     return np.concatenate(rows_all), torch.cat(ref_all), torch.cat(bnd_all)
 
 
-def attention_windows(B, H, W, ws, seed, nrand=6):
-    """Every border window of the first and the last image (the shifted-mask windows are the last row / column), plus random ones."""
+def attention_windows(B, H, W, ws, seed, nrand=6, images=()):
+    """Every border window of the first and the last image (the shifted-mask windows are the last row / column) and of `images`,
+    plus random ones."""
     nwy, nwx = H // ws, W // ws
     s = set()
-    for n in sorted({0, B - 1}):
+    for n in sorted({0, B - 1} | {int(n) for n in images if 0 <= n < B}):
         for wy in range(nwy):
             s |= {(n, wy, 0), (n, wy, nwx - 1)}
         for wx in range(nwx):
@@ -334,6 +356,39 @@ def sub_batches(B, S):
     return sorted({q + (1 if i < r else 0) for i in range(min(S, B))})
 
 
+# ---------------------------------------------------------------- the launches the CLI and the Python API make by default
+CLI_TILE, CLI_PAD, MAX_TILE_BATCH = 240, 16, 16           # inference.py / FeMaSRNet.test_tile defaults, FeMaSRNet.max_tile_batch
+PRODUCT_STREAMS = (1, 2, 3)                               # num_streams: the module's default, two, the CLI's default
+_X4 = dict(codebook_params=[[32, 1024, 512]], LQ_stage=True, scale_factor=4)
+_X2 = dict(codebook_params=[[32, 1024, 512]], LQ_stage=True, scale_factor=2)
+
+
+def tiled_calls(height, width, tile_size=CLI_TILE, tile_pad=CLI_PAD, max_tile_batch=MAX_TILE_BATCH):
+    """{(h, w) window class: sorted sizes of the batched test() calls FeMaSRNet._tiled makes on one image} (one rank)."""
+    from femasr_amd import tiling
+    out = {}
+    for hw, tl in tiling.shape_classes(tiling.enumerate_tiles(height, width, tile_size, tile_pad)).items():
+        out[hw] = sorted({len(tl[i:i + max_tile_batch]) for i in range(0, len(tl), max_tile_batch)})
+    return out
+
+
+def _product_workloads():
+    """Derived, not typed in: the tiled branch on a 1440x1440 and a 1356x2040 image (every window class, every batched call, its
+    sub-batches at 1, 2 and 3 streams) and the whole-image branch (h*w < 600^2) at B = 1."""
+    W = {}
+    for (ih, iw) in ((1440, 1440), (1356, 2040)):
+        for (h, w), calls in tiled_calls(ih, iw).items():
+            subs = sorted({b for c in calls for s in PRODUCT_STREAMS for b in sub_batches(c, s)})
+            W[f'tiled{ih}x{iw}_win{h}x{w}'] = dict(cfg=_X4, hw=(h, w), fn='test', sub_batches=subs, calls=calls)
+    for (h, w) in ((599, 599), (339, 510), (16, 600)):
+        W[f'whole{h}x{w}_x4'] = dict(cfg=_X4, hw=(h, w), fn='test', sub_batches=[1], calls=[1])
+    W['whole599x599_x2'] = dict(cfg=_X2, hw=(599, 599), fn='test', sub_batches=[1], calls=[1])
+    return W
+
+
+PRODUCT_WORKLOADS = _product_workloads()        # (separate from WORKLOADS: the bench-anchored tests and their ids stay as they are)
+
+
 def _wino_ok(B, H, W, cin, cout, up2):
     # kernels_wino.hip / kernels_wino_up2.hip shape rules at the default limits (32-bit byte offsets)
     if cin % 32 or cout % 64 or cin > 1024:
@@ -344,8 +399,8 @@ def _wino_ok(B, H, W, cin, cout, up2):
 
 
 def workload_layers(cfg, batch, hw, fn, weight_shapes):
-    """The conv / linear layers and the small kernels one sub-batch of the workload runs, in order, with the shapes the network's
-    resolution schedule gives them (femasr_arch.py geometry, model.hip plan_geometry / run_tail) and the channel counts of the
+    """The conv / linear layers and the small kernels one sub-batch of the workload runs, in order, on inputs of hw = side or (h, w)
+    pixels, with the shapes the network's resolution schedule gives them (femasr_arch.py geometry, model.hip plan_geometry / run_tail) and the channel counts of the
     architecture's weights.  Returns a list of dicts; conv entries: key, B, H, W, cin, cout, ksz, stride, pad, up2, pro (GN+SiLU
     prologue), nres, act, behind (decoder side of the single lookup), gn_out (the output feeds a GroupNorm)."""
     lq = cfg['LQ_stage']
@@ -353,11 +408,12 @@ def workload_layers(cfg, batch, hw, fn, weight_shapes):
     gt, cbs = 256, cfg['codebook_params'][0][0]
     max_depth = int(math.log2(gt // cbs))
     enc_depth = int(math.log2(gt // sf // cbs))
+    h_in, w_in = (hw, hw) if isinstance(hw, int) else hw
     if fn == 'test':
         wsz = 8 // sf * 8
-        H = (hw // wsz + 1) * wsz
+        H, W = (h_in // wsz + 1) * wsz, (w_in // wsz + 1) * wsz
     else:
-        H = hw
+        H, W = h_in, w_in
     B = batch
     L = []
 
@@ -376,9 +432,9 @@ def workload_layers(cfg, batch, hw, fn, weight_shapes):
         L.append(dict(kind='gn', B=B, H=H, W=W, c=c, key=p + '.conv.3.norm'))
         conv(p + '.conv.5', H, W, c, pro=True, nres=1 + nres2, behind=behind, gn_out=gn_out)
 
-    L.append(dict(kind='pad', B=B, H=H, W=H, c=3, h_in=hw))
+    L.append(dict(kind='pad', B=B, H=H, W=W, c=3, h_in=h_in, w_in=w_in, Hp=H, Wp=W))
     e = 'multiscale_encoder'
-    h, w, c = conv(e + '.in_conv', H, H, 3, ksz=4, pad=1)
+    h, w, c = conv(e + '.in_conv', H, W, 3, ksz=4, pad=1)
     feats = []
     bi = 0
     for i in range(enc_depth):

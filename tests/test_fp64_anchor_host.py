@@ -222,3 +222,160 @@ def test_conv_variant_hook_names_and_refusals():
     a.w_wino, a.w_bf16s, a.prologue, a.res1 = None, 1, 0, None
     _lib.check(lib.femasr_debug_conv_variant_name(ctypes.byref(a), buf, len(buf)))
     assert buf.value.decode() == 'conv3x3_bf16s<128px x128,9Cin split GEMM,nres=0>'
+
+
+# ---------------------------------------------------------------- the launch inventories (host: the variant hook needs no GPU)
+# sha256 of repr(workload_layers(...)) per sub-batch and of the sorted conv case keys of inventory(), as computed before
+# workload_layers took rectangular inputs (the pad entry's new w_in / Hp / Wp fields left out of the layer digest)
+BENCH_PINS = {
+    'x4_b16_128': ({5: '822b1c42561b97fbf2f60ef74556a9033ec34732bcbca7124d87c74c1663f70a',
+                    6: 'b12619c5ecea4ce05821ad18fab3cfa3993c6a0670cc8131118d5fc0e59c5b1e'},
+                   '124cb55adb9a16cd54719dfec9150361681af7f283688d28ca5ab075750f62b9', 68, 20),
+    'x2_b32_256': ({10: '9df8b635732f56be10a0e256ffdb2eee7014d5f9a79d2c07481671d3fffac1cc',
+                    11: 'd468e3db67389cf9f956c057bd85e7c6884e1be2cc99a1b069a8a3cc518788c0'},
+                   'e6bbc84ca2e5e51d97a328c53f4010fc105ed9cfebf2a958805e9562ba9a7eca', 76, 20),
+    'hq_b8_512': ({2: '3397daec009b7ddc6e6af8d798dc1a6417846cb6f8f469486ab5afeb8b839860',
+                   3: '2bd175bda29ac8a5d5f23650f081b571952eec0c2e00d6e8d6f37dcd548f4bbf'},
+                  'fb20f7ac81ac2d67fcd0a098833b99009ba3facf480d2d241c34ea6080f3b8d9', 74, 14),
+}
+
+
+def _digest(obj):
+    import hashlib
+    return hashlib.sha256(repr(obj).encode()).hexdigest()
+
+
+@pytest.mark.parametrize('wl_name', list(R.WORKLOADS))
+def test_bench_inventory_unchanged_by_rectangular_layers(wl_name):
+    import anchor_cases as A
+    layers, conv_keys, nconv, nsmall = BENCH_PINS[wl_name]
+    assert R.sub_batches(R.WORKLOADS[wl_name]['batch'], R.BENCH_STREAMS) == sorted(layers)
+    for sub_b, want in layers.items():
+        L = [{k: v for k, v in l.items() if not (l['kind'] == 'pad' and k in ('w_in', 'Hp', 'Wp'))} for l in A._layers(wl_name, sub_b)]
+        assert _digest(L) == want, (wl_name, sub_b)
+    convs, small = A.inventory(wl_name)
+    assert (_digest(sorted(convs)), len(convs), len(small)) == (conv_keys, nconv, nsmall)
+    for l in A._layers(wl_name, sorted(layers)[0]):
+        if l['kind'] == 'pad':
+            assert (l['Hp'], l['Wp'], l['w_in']) == (l['H'], l['W'], l['h_in'])
+
+
+def test_product_workloads_are_the_cli_defaults():
+    """The table is derived from tiling.enumerate_tiles / shape_classes at (240, 16), max_tile_batch 16, streams 1, 2, 3."""
+    from femasr_amd.archs.femasr_arch import FeMaSRNet
+    import inspect
+    sig = inspect.signature(FeMaSRNet.test_tile).parameters
+    assert (sig['tile_size'].default, sig['tile_pad'].default) == (R.CLI_TILE, R.CLI_PAD)
+    assert R.tiled_calls(1440, 1440) == {(256, 256): [4], (256, 272): [8], (272, 256): [8], (272, 272): [16]}
+    big = R.tiled_calls(1356, 2040)
+    assert big[(272, 272)] == [12, 16] and (172, 136) in big and (272, 136) in big
+    W = R.PRODUCT_WORKLOADS
+    assert W['tiled1440x1440_win272x272']['sub_batches'] == [5, 6, 8, 16]
+    assert W['tiled1356x2040_win272x272']['sub_batches'] == [4, 5, 6, 8, 12, 16]
+    assert not set(W) & set(R.WORKLOADS)
+    for n in ('whole599x599_x4', 'whole339x510_x4', 'whole16x600_x4', 'whole599x599_x2'):
+        assert W[n]['sub_batches'] == [1] and W[n]['hw'][0] * W[n]['hw'][1] < 600 * 600
+
+
+def _out_bytes(case):
+    import anchor_cases as A
+    L = case['L']
+    a = A._conv_args(L, case['form'], case['fast'])
+    return 4 * L['B'] * a.Ho * a.Wo * L['cout']
+
+
+def test_product_inventory_conditions():
+    import anchor_cases as A
+    convs, small = A.product_inventory()
+    assert convs and small
+    bench = set()
+    for wl in R.WORKLOADS:
+        bench |= set(A.inventory(wl)[0])
+    assert not set(convs) & bench                               # only launches the bench inventory does not hold
+    cases = list(convs.values())
+
+    def has(pred):
+        return any(pred(c) for c in cases)
+    halo = lambda c: c['form'] == 'direct' and c['slot'].startswith('conv3x3_halo<')
+    assert has(lambda c: c['form'] == 'wino4') and has(lambda c: c['form'] == 'wino_up2')
+    assert has(lambda c: halo(c) and 'up2=false' in c['slot'])
+    assert has(lambda c: halo(c) and 'up2=true' in c['slot'] and c['L']['up2'])          # x2 as 4 phase filters
+    assert has(lambda c: c['form'] == 'split3x3') and has(lambda c: c['form'] == 'split1x1')
+    assert has(lambda c: c['form'] == 'direct' and c['L']['ksz'] == 4 and c['L']['cin'] == 3)     # in_conv (fp32 implicit GEMM)
+    assert has(lambda c: c['slot'].startswith('conv3x3_cout3<') and c['L']['key'] == 'out_conv')
+    assert has(lambda c: c['L']['kind'] == 'conv' and c['L']['ksz'] == 3 and c['L']['H'] != c['L']['W'])     # rectangular
+    assert any(L['kind'] == 'attn' and L['H'] != L['W'] for L in small.values())
+    assert any(L['kind'] == 'pad' and L['Hp'] != L['Wp'] for L in small.values())
+    assert any(L['kind'] == 'ln' and L['rows'] == 16 * 144 * 144 for L in small.values())
+    nb = [_out_bytes(c) for c in cases]
+    assert any(b > 2 ** 32 for b in nb)
+    assert any(2 ** 31 < b < 2 ** 32 for b in nb)
+    assert any(0.9 * 2 ** 31 <= b < 2 ** 31 for b in nb)
+    # the whole-image branch at 599x599 (608^2 after test()'s pad): the mixed plan on both sides of the Winograd per-image limit
+    w599, _ = A.inventory('whole599x599_x4')
+    res = [c for c in w599.values() if c['L']['pro'] and c['L']['behind']]
+    got = {(c['L']['cin'], c['L']['H'], c['form'], c['slot'].split('<')[0]) for c in res}
+    assert (256, 608, 'wino4', 'conv3x3_wino4') in got
+    assert (128, 1216, 'direct', 'conv3x3_halo') in got and (64, 2432, 'direct', 'conv3x3_halo') in got
+    assert not any(c['form'] == 'wino4' and c['L']['cin'] < 256 for c in res)
+    up = {(c['L']['cout'], c['form'], 'up2=true' in c['slot']) for c in w599.values() if c['L']['up2'] and c['L']['cout'] in (128, 64)}
+    assert up == {(128, 'direct', True), (64, 'direct', True)}
+
+
+def test_positions_cover_the_images_where_offsets_wrap():
+    """B = 16 of 1152^2 x 64 fp32 (5.4 GB): a multiple of 2^31 bytes falls into images 6 and 12; B = 8: image 6; under 2^31: none."""
+    ib = 1152 * 1152 * 64 * 4
+    assert R.straddle_images(6, ib) == [] and R.straddle_images(8, ib) == [6, 7] and R.straddle_images(16, ib) == [6, 7, 12, 13]
+    for B in (8, 16):
+        for k in range(1, B * ib // 2 ** 31 + 1):
+            n = k * 2 ** 31 // ib
+            assert n * ib <= k * 2 ** 31 < (n + 1) * ib and n in R.straddle_images(B, ib) and min(n + 1, B - 1) in R.straddle_images(B, ib)
+    assert R.straddle_images(4, 2 ** 30) == [1, 2, 3]           # the boundary is an image seam: the image before, at and after it
+    imgs = R.straddle_images(16, ib)
+    pos = R.conv_positions(16, 1152, 1152, 3, images=imgs)
+    for n in [0, 15] + imgs:
+        p = pos[pos[:, 0] == n]
+        ys, xs = set(p[:, 1].tolist()), set(p[:, 2].tolist())
+        assert {0, 1151} <= ys and {0, 1151} <= xs, n                                    # corners and borders
+        assert {7, 8, 15, 16, 1144, 1151} & ys and {15, 16, 1136, 1151} & xs, n          # tile seams, the last tile
+        have = set(map(tuple, p[:, 1:].tolist()))           # the whole structured grid (no subsampling at six images)
+        assert all((y, x) in have for y in R.axis_samples(1152, (8, 16)) for x in R.axis_samples(1152, (16,))), n
+    # without images= the sampling is what it was: first and last image only
+    old = R.conv_positions(16, 1152, 1152, 3)
+    assert len(old[(old[:, 0] != 0) & (old[:, 0] != 15)]) <= 64
+    wins = R.attention_windows(16, 72, 72, 8, 1, images=imgs)
+    assert {n for n, _, _ in wins} >= set([0, 15] + imgs)
+
+
+def test_halo_kernels_leave_at_2_to_31_input_elements():
+    """The halo form, the out_conv kernel and the bf16x3 halo form hold the input patch offset as a 32-bit ELEMENT offset; the
+    shape rule they share (femasr_conv_halo_eligible / femasr_conv_bf16x3_shape_ok: B*H*W*Cin < 2^31) sends a larger input to the
+    generic implicit-GEMM form, which indexes with 64 bits, or refuses (bf16x3: before any HIP call) - marker pointers only."""
+    import ctypes
+    from femasr_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+
+    def name(B, H, W, cin, cout, up2=0, pro=0):
+        a = _lib.ConvArgs()
+        a.B, a.H, a.W, a.Cin, a.Cout, a.ksz, a.stride, a.pad, a.up2, a.prologue = B, H, W, cin, cout, 3, 1, 1, up2, pro
+        a.Ho, a.Wo = (2 * H, 2 * W) if up2 else (H, W)
+        a.w, a.w_up2 = 1, (1 if up2 else None)
+        _lib.check(lib.femasr_debug_conv_variant_name(ctypes.byref(a), buf, len(buf)))
+        return buf.value.decode()
+    # 64 channels x 2048^2 = 2^28 elements per image: 7 images are under 2^31 elements, 8 are at it
+    assert name(7, 2048, 2048, 64, 64, pro=1).startswith('conv3x3_halo<')
+    assert name(7, 2048, 2048, 64, 3).startswith('conv3x3_cout3<')
+    assert name(7, 2048, 2048, 64, 64, up2=1).startswith('conv3x3_halo<') and 'up2=true' in name(7, 2048, 2048, 64, 64, up2=1)
+    for B in (8, 16, 18, 256):          # 2^31, 2^32, past 2^32 (the unsigned wrap), far past it
+        for kw in (dict(cout=64, pro=1), dict(cout=3), dict(cout=64, up2=1)):
+            n = name(B, 2048, 2048, 64, **kw)
+            assert n.startswith('conv_igemm<'), (B, kw, n)
+    # the example of a public knob set too high: 256 tiles of 128^2, out_conv input 256 x 576^2 x 64 = 5.4 G elements
+    assert name(256, 576, 576, 64, 3).startswith('conv_igemm<')
+    a = _lib.ConvArgs()
+    a.B, a.H, a.W, a.Cin, a.Cout, a.ksz, a.stride, a.pad, a.Ho, a.Wo = 8, 2048, 2048, 64, 64, 3, 1, 1, 2048, 2048
+    a.in_, a.w, a.bias, a.out, a.w_bf16x3 = 1, 1, 1, 1, 1
+    assert lib.femasr_conv2d(None, ctypes.byref(a)) != 0 and b'bf16x3' in lib.femasr_last_error()
+    a.B = 7
+    _lib.check(lib.femasr_debug_conv_variant_name(ctypes.byref(a), buf, len(buf)))      # eligible below the limit
