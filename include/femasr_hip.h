@@ -166,8 +166,10 @@ typedef struct {
     int32_t Ho, Wo;
     const void *w_bf16x3; /* optional: femasr_repack_oihw_bf16x3 weights.  When non-NULL and the layer is a 3x3
                              stride-1 pad-1 conv with Cin % 32 == 0 (no LN prologue / GELU) it runs on the bf16
-                             matrix cores with the 3-term hi/lo split (~1e-5 relative, NOT bit-exact); NULL =
-                             exact fp32 */
+                             matrix cores with the 3-term hi/lo split (NOT bit-exact: every output element is within
+                             128 * 2^-24 * sum_k |t_k w_k| of the exact conv - t the activated input -, plus the fp32
+                             roundings of bias / residuals and the prologue SiLU's 8 ulp; tests/fp64_ref.py
+                             C_FORM['bf16x3'], tests/test_gpu_mode_anchor.py); NULL = exact fp32 */
     double *gn_part;      /* optional, 3x3 stride-1 halo convs (exact fp32 and bf16x3): per-(sample, 8x16 tile, group)
                              partial GroupNorm(32) moments (sum, sum of squares) of the OUTPUT,
                              [B][tilesY*tilesX][32][2] doubles, for femasr_gn_coeffs_from_partials (saves the separate
@@ -207,7 +209,8 @@ typedef struct {
 /* Size limits (each a shape rule evaluated before any launch; DESIGN.md 5.7, tests/test_gpu_product_anchor.py):
  *   rows B*Ho*Wo < 2^31 - 256 for every form, else FEMASR_ERR_INVALID;
  *   w_wino: < 2^31 elements per tensor and < 2^27 per image (32-bit byte offsets), else FEMASR_ERR_INVALID;
- *   w_bf16x3 and the 3x3 form of w_bf16s: B*H*W*Cin < 2^31, else FEMASR_ERR_INVALID;
+ *   w_bf16x3: B*H*W*Cin < 2^31 and B*Ho*Wo*Cout < 2^31 (tests/test_gpu_mode_anchor.py), the 3x3 form of w_bf16s: B*H*W*Cin < 2^31,
+ *   else FEMASR_ERR_INVALID;
  *   the direct form (none of those weights given): the 3x3 stride-1 halo kernels and the Cout = 3 kernel hold the input patch
  *   offset as a 32-bit ELEMENT offset and are used while B*H*W*Cin < 2^31; a larger input - 2^32 elements and more included - runs
  *   on the generic implicit GEMM, whose offsets are 64-bit (slower; gn_part is then not accepted).  Nothing wraps silently. */

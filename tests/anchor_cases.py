@@ -1,5 +1,6 @@
 """Shared machinery of the fp64-anchor GPU tests (tests/test_gpu_fp64_anchor.py: the benchmarked workloads;
-tests/test_gpu_product_anchor.py: the launches the CLI and the Python API make by default, and the kernels' offset limits).
+tests/test_gpu_product_anchor.py: the launches the CLI and the Python API make by default, and the kernels' offset limits;
+tests/test_gpu_mode_anchor.py: the non-default arithmetic modes - MODES, mode_inventory, BF16X3_UNIT - at both sets of shapes).
 
 inventory() lists the distinct (instantiation, launch shape) cases of a workload table - the instantiation name comes from the library
 itself (femasr_debug_conv_variant_name, which needs no GPU) - and run_conv_case / run_small_case launch one case through the public
@@ -39,12 +40,12 @@ def _workload(wl_name):
     return R.WORKLOADS[wl_name] if wl_name in R.WORKLOADS else R.PRODUCT_WORKLOADS[wl_name]
 
 
-def _layers(wl_name, sub_b):
+def _layers(wl_name, sub_b, decoder_math='fp32'):
     wl = _workload(wl_name)
     key = repr(sorted(wl['cfg'].items()))
     if key not in _SHAPES:
         _SHAPES[key] = _weight_shapes(wl['cfg'])
-    return R.workload_layers(wl['cfg'], sub_b, wl['hw'], wl['fn'], _SHAPES[key])
+    return R.workload_layers(wl['cfg'], sub_b, wl['hw'], wl['fn'], _SHAPES[key], decoder_math)
 
 
 def _conv_args(L, form, fast_act):
@@ -64,6 +65,8 @@ def _conv_args(L, form, fast_act):
         a.fast_act = int(fast_act)
     if form in ('split3x3', 'split1x1'):
         a.w_bf16s = 1
+    if form == 'bf16x3':
+        a.w_bf16x3 = 1
     if L['up2'] and form == 'direct':
         a.w_up2 = 1
     if form == 'wino_up2' and L['in_add']:
@@ -84,6 +87,8 @@ def _gn_tiles(form, a):
     halo = a.ksz == 3 and a.stride == 1 and a.pad == 1 and a.Cin % 32 == 0 and a.act in (0, 2) and not (a.up2 and a.prologue)
     if form in ('split3x3', 'split1x1') or not fus:
         return 0
+    if form == 'bf16x3':          # per 8x16 tile of the output (full resolution for an x2 conv), at most 8 channels per group
+        return ((a.Ho + 7) // 8) * ((a.Wo + 15) // 16) if c <= 256 else 0
     if form in ('wino4', 'wino_up2'):
         return ((a.Ho + 15) // 16) * ((a.Wo + 15) // 16) if halo else 0
     if not halo:
@@ -91,24 +96,29 @@ def _gn_tiles(form, a):
     return 4 * ((a.H + 7) // 8) * ((a.W + 15) // 16) if a.up2 else ((a.Ho + 7) // 8) * ((a.Wo + 15) // 16)
 
 
-def inventory(wl_name, modes=('fp32', 'fp32_strict'), linear_math='bf16_split', sub_batches=None):
+def inventory(wl_name, modes=('fp32', 'fp32_strict'), linear_math='bf16_split', sub_batches=None, split_res2=False):
     """Distinct (instantiation, launch shape) conv cases and the small-kernel cases of one workload: {key: case}.
-    sub_batches: only these of the workload's sub-batch sizes."""
+    sub_batches: only these of the workload's sub-batch sizes.  split_res2: a conv with two residuals is a case of its own (the
+    names of the halo, bf16x3 and GEMM instantiations do not tell the residual count; the mode inventories ask for it)."""
     wl = _workload(wl_name)
     convs, small = {}, {}
     subs = wl.get('sub_batches') or R.sub_batches(wl['batch'], R.BENCH_STREAMS)
     assert sub_batches is None or set(sub_batches) <= set(subs), (wl_name, sub_batches, subs)
     for sub_b in (subs if sub_batches is None else sorted(sub_batches)):
-        for L in _layers(wl_name, sub_b):
-            if L['kind'] != 'conv':
+        per_mode = [_layers(wl_name, sub_b, dm) for dm in modes]          # (the skip schedule follows the mode; same layers, same order)
+        for Ls in zip(*per_mode):
+            if Ls[0]['kind'] != 'conv':
+                L = Ls[0]
                 small.setdefault((L['kind'],) + tuple(sorted((k, v) for k, v in L.items() if k not in ('kind', 'key'))), L)
                 continue
-            for dm in modes:
+            for dm, L in zip(modes, Ls):
                 form = R.conv_form(L, dm, linear_math)
                 fast = dm == 'fp32' and form in ('wino4', 'wino_up2')
                 a = _conv_args(L, form, fast)
                 name = _slot(a)
                 key = (name, L['B'], L['H'], L['W'], L['cin'], L['cout'], L['ksz'], L['stride'], L['in_add'], L['gn_out'])
+                if split_res2 and L['nres'] == 2:
+                    key += ('res2',)
                 convs.setdefault(key, dict(L=L, form=form, fast=fast, slot=name))
     return convs, small
 
@@ -128,6 +138,55 @@ def product_inventory(names=None):
         for k, v in s.items():
             small.setdefault(k, v)
     return convs, small
+
+
+# ---------------------------------------------------------------- the non-default arithmetic modes
+MODES = (('bf16x3', 'bf16_split'), ('fp32_direct', 'bf16_split'), ('fp32', 'fp32'))          # (decoder_math, linear_math)
+MODE_PRODUCT = {'tiled1440x1440_win272x272': (16, 6), 'whole599x599_x4': None}                 # the product shapes the mode module launches
+
+
+def mode_inventory(names, decoder_math, linear_math):
+    """The cases of the workloads `names` (a list, or {name: sub-batch sizes or None}) under one non-default mode that neither the
+    benchmarked workloads' default inventories nor the default inventories of `names` hold (those run in the other two modules)."""
+    default, default_small = set(), set()
+    for wl in R.WORKLOADS:
+        c, s = inventory(wl)
+        default |= set(c)
+        default_small |= set(s)
+    convs, small = {}, {}
+    for n in names:
+        subs = names[n] if isinstance(names, dict) else None
+        if n not in R.WORKLOADS:
+            c, s = inventory(n, sub_batches=subs)
+            default |= set(c)
+            default_small |= set(s)
+        c, s = inventory(n, modes=(decoder_math,), linear_math=linear_math, sub_batches=subs, split_res2=True)
+        for k, v in c.items():
+            if k not in default:
+                convs.setdefault(k, v)
+        for k, v in s.items():
+            if k not in default_small:
+                small.setdefault(k, v)
+    return convs, small
+
+
+def make_case(form, B, H, W, cin, cout, up2=False, pro=False, nres=0, gn_out=False, fast=False, key=None):
+    """A 3x3 stride-1 conv case outside the workload tables (unit shapes, limit shapes)."""
+    L = dict(kind='conv', key=key or f'unit {form}', B=B, H=H, W=W, cin=cin, cout=cout, ksz=3, stride=1, pad=1, up2=up2, pro=pro, nres=nres,
+             act=0, behind=True, gn_out=gn_out, in_add=False)
+    return dict(L=L, form=form, fast=fast, slot=_slot(_conv_args(L, form, fast)))
+
+
+# The 12 instantiations femasr_conv_bf16x3_pick_variant can return (g_v16 rows 0-2, 6-11, 15-17).  The network's layers behind the
+# lookup reach seven of them; no conv there has Cout <= 32, and none with 33 .. 128 output channels is without both a prologue and x2
+# (tests/test_fp64_anchor_host.py::test_bf16x3_instantiations_are_all_launched derives that).  Those five get unit shapes at the
+# bench workload's grid sizes, B = 6: ragged last tiles, one or two residuals, fused GroupNorm partials.
+def bf16x3_unit_cases():
+    return [make_case('bf16x3', 6, 288, 288, 128, 128, nres=1, gn_out=True, key='unit bf16x3 128 plain'),
+            make_case('bf16x3', 6, 570, 566, 64, 64, nres=2, key='unit bf16x3 64 plain'),
+            make_case('bf16x3', 6, 570, 566, 64, 32, nres=1, gn_out=True, key='unit bf16x3 32 plain'),
+            make_case('bf16x3', 6, 576, 576, 64, 32, pro=True, nres=2, gn_out=True, key='unit bf16x3 32 gn'),
+            make_case('bf16x3', 6, 285, 283, 64, 32, up2=True, gn_out=True, key='unit bf16x3 32 x2')]
 
 
 # ---------------------------------------------------------------- launches through the public unit ABI
@@ -154,6 +213,10 @@ def _pack(form, L, w_oihw):
         t = torch.empty(int(lib.femasr_packed_weight_bf16s_bytes(o, i)), dtype=torch.uint8, device='cuda')
         _lib.check(lib.femasr_repack_k1_bf16s(None, _lib.ptr(w_oihw.reshape(o, i)), o, i, _lib.ptr(t)))
         packed['w_bf16s'] = t
+    if form == 'bf16x3':
+        t = torch.empty(int(lib.femasr_packed_weight_bf16x3_bytes(o, i, kh, kw)), dtype=torch.uint8, device='cuda')
+        _lib.check(lib.femasr_repack_oihw_bf16x3(None, _lib.ptr(w_oihw), o, i, kh, kw, _lib.ptr(t)))
+        packed['w_bf16x3'] = t
     if form == 'split3x3':
         t = torch.empty(int(lib.femasr_packed_weight_conv3x3_bf16s_bytes(o, i)), dtype=torch.uint8, device='cuda')
         _lib.check(lib.femasr_repack_oihw_bf16s(None, _lib.ptr(w_oihw), o, i, _lib.ptr(t)))
@@ -236,6 +299,7 @@ def run_conv_case(case, seed, wrap=False, batch_check=False):
     a.w_up2 = packed['w_up2'].data_ptr() if 'w_up2' in packed else None
     a.w_wino = packed['w_wino'].data_ptr() if 'w_wino' in packed else None
     a.w_bf16s = packed['w_bf16s'].data_ptr() if 'w_bf16s' in packed else None
+    a.w_bf16x3 = packed['w_bf16x3'].data_ptr() if 'w_bf16x3' in packed else None
     a.in_add = in_add.data_ptr() if in_add is not None else None
     tiles = _gn_tiles(form, a) if L['gn_out'] else 0
     part = None
@@ -254,10 +318,11 @@ def run_conv_case(case, seed, wrap=False, batch_check=False):
                 images |= set(R.straddle_images(B, t[0].numel() * 4))
     pos = R.conv_positions(B, ho, wo, seed, tiles_y=(8, 16), tiles_x=(16,), images=images)
     ref, mag, pro_t, rest = R.conv_ref(x, w.cpu().numpy(), bias.cpu().numpy(), pos, L['ksz'], L['stride'], L['pad'], L['up2'],
-                                       pro=pro, fast_act=fast, in_add=in_add, res=res, act=L['act'])
+                                       pro=pro, fast_act=fast or form == 'bf16x3', in_add=in_add, res=res, act=L['act'])
     p = torch.as_tensor(pos, device='cuda')
     got = out[p[:, 0], p[:, 1], p[:, 2]].cpu()
-    cform = 'gemm_fp32' if (form == 'direct' and L['cin'] % 32) else form
+    # the fp32 GEMM kernels: the generic implicit GEMM of a Cin % 32 != 0 layer (in_conv) and the LDS-DMA GEMM of the 1x1 layers
+    cform = 'gemm_fp32' if (form == 'direct' and (L['cin'] % 32 or R.gemm_fp32_layer(L))) else form
     worst = R.check(got, ref, R.conv_bound(mag, pro_t, rest, cform), what)
     _note(case['slot'], worst)
     if part is not None:        # fused GroupNorm partials -> coefficients, against fp64 moments of the kernel's own output
@@ -274,7 +339,7 @@ def run_conv_case(case, seed, wrap=False, batch_check=False):
             a1 = _conv_args(L1, form, fast)
             out1 = torch.full((1, ho, wo, cout), float('nan'), dtype=torch.float32, device='cuda')
             a1.in_, a1.w, a1.bias, a1.out = xin[n].data_ptr(), a.w, a.bias, out1.data_ptr()
-            a1.w_up2, a1.w_wino, a1.w_bf16s = a.w_up2, a.w_wino, a.w_bf16s
+            a1.w_up2, a1.w_wino, a1.w_bf16s, a1.w_bf16x3 = a.w_up2, a.w_wino, a.w_bf16s, a.w_bf16x3
             a1.res1 = res[0][n].data_ptr() if len(res) >= 1 else None
             a1.res2 = res[1][n].data_ptr() if len(res) >= 2 else None
             a1.in_add = in_add[n].data_ptr() if in_add is not None else None

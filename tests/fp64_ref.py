@@ -18,15 +18,27 @@ Bounds, per element, u = 2^-24:
 C_FORM calibration (tests/test_fp64_anchor_host.py::test_calibration, the CPU oracle - bit-identical to each strict-mode kernel - at
 the network's channel counts on reduced grids; worst ratio = max over elements of the c the element needs):
   form         K                worst c   C_FORM
-  direct       9*64, 9*256        4.0        16
+  direct       9*64, 9*256        4.0        20    (16 until the stride-2 row below was calibrated)
+  direct x2    9*256, 9*128       2.3        20    (nearest-x2 as four phase filters; decoder_math 'fp32_direct', linear_math 'fp32')
+  direct s2    9*64, 9*128        4.09       20    (stride 2, the generic implicit GEMM; linear_math 'fp32')
   wino4        9*64 .. 9*256     48.7       256
   wino_up2     9*128, 9*256      61.4       256
   split3x3     9*256              1.4         8
   split1x1     256, 1024          1.2         8
-  gemm_fp32    48 (Cin 3, k4)     3.0        16
+  gemm_fp32    48 (Cin 3, k4)     3.0        20    (16 until the 1x1 rows below were calibrated)
+  gemm_fp32    256, 1024 (1x1)    4.42       20    (the LDS-DMA GEMM at qkv 256->768 - the worst -, proj, fc1 + GELU, fc2 1024->256,
+                                                    before_quant 256->512; linear_math 'fp32')
+  bf16x3       9*64 .. 9*512     27.1       128    (against the CPU MODEL of the specified arithmetic, test_bf16x3_model_calibrates_its_
+                                                    constant: N(0,1) inputs 19.4 / 15.7 / 14.9 / 9.6 and SiLU-shaped inputs 27.1 / 21.9 /
+                                                    16.5 / 9.1 at Cin 64 / 128 / 256 / 512; never above C_BF16X3_MAX = 208, the analytic
+                                                    worst case: 3 x 2^-18 for the two representation errors and the dropped lo*lo term,
+                                                    + 16 for the fp32 accumulation.  What the GPU needs of it - the matrix instruction's
+                                                    own accumulation - is NOT MEASURED yet: tests/test_gpu_mode_anchor.py prints the
+                                                    worst err / bound per slot in its last test)
 Every constant is >= 4x the worst calibrated ratio (the host test asserts it).  One bf16 rounding of the operands (no split) is
 rejected by every form's constant (test_conv_bound_rejects_wrong_reference), so the constants separate fp32-grade results from
-bf16-grade ones.  The Winograd forms need ~10-15x the direct form's c: the transforms' rounding, not a defect.
+bf16-grade ones; the bf16x3 constant also rejects the model with either cross term (hi*lo, lo*hi) left out, at Cin 64 and 512, with
+more than half of the elements over their own bound (test_bf16x3_bound_rejects_a_missing_cross_term).  The Winograd forms need ~10-15x the direct form's c: the transforms' rounding, not a defect.
 """
 import math
 
@@ -34,8 +46,11 @@ import numpy as np
 import torch
 
 U = 2.0 ** -24
-C_FORM = {'direct': 16.0, 'wino4': 256.0, 'wino_up2': 256.0, 'split3x3': 8.0, 'split1x1': 8.0, 'gemm_fp32': 16.0}
-PRO_ERR = {False: 3.0, True: 8.0}       # SiLU error in ulp of |silu|: IEEE expf / division (exact), v_exp_f32 + v_rcp_f32 (fast_act)
+C_FORM = {'direct': 20.0, 'wino4': 256.0, 'wino_up2': 256.0, 'split3x3': 8.0, 'split1x1': 8.0, 'gemm_fp32': 20.0, 'bf16x3': 128.0}
+C_BF16X3_MAX = 3 * 2.0 ** -18 / 2.0 ** -24 + 16.0     # 208: two representation errors + the dropped lo*lo term, + 16 for the fp32 accumulation:
+                                                      # frozen at that figure on purpose (the tighter cap); it does not follow C_FORM['direct']
+PRO_ERR = {False: 3.0, True: 8.0}       # SiLU error in ulp of |silu|: IEEE expf / division (exact), v_exp_f32 + v_rcp_f32 (fast_act,
+                                        # and the bf16x3 kernels' prologue in every mode)
 C_GN, C_LN, C_ATTN = 16.0, 16.0, 16.0
 NEAR_TIE_ULP = 4.0                      # oracle/near_tie.py (the one near-tie rule of the parity checks)
 
@@ -162,6 +177,7 @@ def conv_ref(x, w_oihw, bias, pos, ksz, stride=1, pad=1, up2=False, pro=None, fa
 
 
 def conv_bound(mag, pro_term, rest, form):
+    """(form 'bf16x3': evaluate conv_ref with fast_act=True - the kernel's prologue SiLU is the hardware one in every mode.)"""
     return C_FORM[form] * U * mag + 2.0 * U * rest + pro_term
 
 
@@ -177,6 +193,20 @@ def check(got, ref, bound, what):
         raise AssertionError(f'{what}: err / bound = {worst:.3g} at {idx}: got {float(got.reshape(-1)[i])!r} '
                              f'ref {float(ref.reshape(-1)[i])!r} bound {float(bound.reshape(-1)[i]):.3e}')
     return worst
+
+
+def check_whole_conv3x3(x, w_khwc, bias, got, form, up2=False, pro=None, res=(), what='conv'):
+    """Every element of a small 3x3 stride-1 pad-1 conv output `got` (B, Ho, Wo, Cout) against fp64 with the per-element bound of
+    `form` (numpy inputs; w_khwc [3][3][Cin][Cout] as the unit tests hold it; res: the residual arrays given, None entries skipped).
+    Returns the worst err / bound."""
+    B, Ho, Wo, _ = got.shape
+    n, y, xx = np.meshgrid(np.arange(B), np.arange(Ho), np.arange(Wo), indexing='ij')
+    pos = np.stack([n.reshape(-1), y.reshape(-1), xx.reshape(-1)], 1).astype(np.int64)
+    rs = [torch.as_tensor(np.asarray(r, np.float32)) for r in res if r is not None]
+    ref, mag, pt, rest = conv_ref(torch.as_tensor(np.asarray(x, np.float32)), np.asarray(w_khwc, np.float32).transpose(3, 2, 0, 1),
+                                  bias, pos, 3, 1, 1, up2, pro=pro, fast_act=form == 'bf16x3', res=rs)
+    g = torch.as_tensor(np.asarray(got, np.float32)).reshape(len(pos), -1)
+    return check(g, ref, conv_bound(mag, pt, rest, form), what)
 
 
 def rejects(fn):
@@ -398,11 +428,21 @@ def _wino_ok(B, H, W, cin, cout, up2):
             and 36 * cin * cout < 2 ** 29)
 
 
-def workload_layers(cfg, batch, hw, fn, weight_shapes):
+def _bf16x3_ok(L):
+    # kernels_conv_bf16.hip femasr_conv_bf16x3_shape_ok (32-bit element offsets into the input and the output)
+    return (L['ksz'] == 3 and L['stride'] == 1 and L['pad'] == 1 and L['cin'] % 32 == 0 and L['cin'] <= 1024 and L['act'] == 0
+            and not (L['up2'] and L['pro']) and L['B'] * L['H'] * L['W'] * L['cin'] < 2 ** 31
+            and L['B'] * L['H'] * L['W'] * (4 if L['up2'] else 1) * L['cout'] < 2 ** 31)
+
+
+def workload_layers(cfg, batch, hw, fn, weight_shapes, decoder_math='fp32'):
     """The conv / linear layers and the small kernels one sub-batch of the workload runs, in order, on inputs of hw = side or (h, w)
     pixels, with the shapes the network's resolution schedule gives them (femasr_arch.py geometry, model.hip plan_geometry / run_tail) and the channel counts of the
     architecture's weights.  Returns a list of dicts; conv entries: key, B, H, W, cin, cout, ksz, stride, pad, up2, pro (GN+SiLU
-    prologue), nres, act, behind (decoder side of the single lookup), gn_out (the output feeds a GroupNorm)."""
+    prologue), nres, act, behind (decoder side of the single lookup), gn_out (the output feeds a GroupNorm).
+    decoder_math decides where the encoder skip of a decoder stage is added (model.hip run_tail): by the NEXT stage's x2 conv while it
+    stages its input (in_add) when that conv runs in the 'wino_up2' form under decoder_math, otherwise as a second residual (nres = 2)
+    of this stage's last conv."""
     lq = cfg['LQ_stage']
     sf = cfg.get('scale_factor', 4) if lq else 1
     gt, cbs = 256, cfg['codebook_params'][0][0]
@@ -484,7 +524,8 @@ def workload_layers(cfg, batch, hw, fn, weight_shapes):
         p = f'decoder_group.{i}.block'
         nxt = lq and i + 1 < max_depth
         h2, w2, c2 = 2 * h, 2 * w, co(p + '.1')
-        next_wino = nxt and _wino_ok(B, h2, w2, c2, co(f'decoder_group.{i + 1}.block.1'), True)
+        next_wino = nxt and conv_form(dict(B=B, H=h2, W=w2, cin=c2, cout=co(f'decoder_group.{i + 1}.block.1'), ksz=3, stride=1, pad=1, up2=True,
+                                           pro=False, act=0, behind=True), decoder_math, 'bf16_split') == 'wino_up2'
         h, w, c = conv(p + '.1', h, w, c, up2=True, behind=True, gn_out=True, in_add=skip_in_next)
         resblock(p + '.2', h, w, c, True, gn_out=True)
         resblock(p + '.3', h, w, c, True, nres2=1 if (nxt and not next_wino) else 0)
@@ -495,8 +536,11 @@ def workload_layers(cfg, batch, hw, fn, weight_shapes):
 
 
 def conv_form(layer, decoder_math, linear_math):
-    """model.hip conv_form for one layer entry: 'wino_up2', 'wino4', 'split3x3', 'split1x1' or 'direct' (+ the GN-apply pass)."""
+    """model.hip conv_form for one layer entry: 'bf16x3', 'wino_up2', 'wino4', 'split3x3', 'split1x1' or 'direct' (+ the GN-apply pass).
+    decoder_math: 'fp32', 'fp32_strict', 'fp32_direct' or 'bf16x3'; linear_math: 'bf16_split' or 'fp32'."""
     L = layer
+    if L['behind'] and decoder_math == 'bf16x3' and L['cout'] > 4 and _bf16x3_ok(L):      # out_conv: the exact VALU kernel in every mode
+        return 'bf16x3'
     if L['behind'] and decoder_math in ('fp32', 'fp32_strict') and L['ksz'] == 3 and L['stride'] == 1 and L['pad'] == 1 and L['act'] == 0:
         if L['up2'] and not L['pro'] and _wino_ok(L['B'], L['H'], L['W'], L['cin'], L['cout'], True):
             return 'wino_up2'

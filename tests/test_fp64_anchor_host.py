@@ -67,7 +67,7 @@ CONV_MUTATIONS = [('drop_border_tap', dict()), ('neighbour_bias', dict()), ('dro
                   ('bf16_operands', dict(cin=256, cout=256, pro=False, nres=0)), ('phase_swap', dict(up2=True, pro=False, nres=0))]
 
 
-@pytest.mark.parametrize('form', ['direct', 'wino4', 'wino_up2', 'split3x3'])
+@pytest.mark.parametrize('form', ['direct', 'wino4', 'wino_up2', 'split3x3', 'bf16x3', 'gemm_fp32'])
 @pytest.mark.parametrize('mutation,kw', CONV_MUTATIONS, ids=[m for m, _ in CONV_MUTATIONS])
 def test_conv_bound_rejects_wrong_reference(form, mutation, kw):
     """The correctly rounded fp64 result passes; the same check against the mutated reference fails."""
@@ -77,13 +77,106 @@ def test_conv_bound_rejects_wrong_reference(form, mutation, kw):
         x, w, b, pro, res, add, (ho, wo) = _conv_case(3, **kw)
         pro = None
     up2 = kw.get('up2', False)
+    fast = form == 'bf16x3'          # (its prologue SiLU is the hardware one in every mode: PRO_ERR[True])
     pos = R.conv_positions(x.shape[0], ho, wo, 4)
-    ref, mag, pt, rest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, up2, pro=pro, res=res)
+    ref, mag, pt, rest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, up2, pro=pro, res=res, fast_act=fast)
     bound = R.conv_bound(mag, pt, rest, form)
     got = _rounded(ref)
     R.check(got, ref, bound, 'correct')
-    bad, bmag, bpt, brest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, up2, pro=pro, res=res, mutate=mutation)
+    bad, bmag, bpt, brest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, up2, pro=pro, res=res, fast_act=fast, mutate=mutation)
     assert R.rejects(lambda: R.check(got, bad, R.conv_bound(bmag, bpt, brest, form), mutation)), mutation
+
+
+# ---------------------------------------------------------------- a CPU model of the specified bf16x3 arithmetic
+def _bf16_split(v):
+    """hi = bf16_rne(v), lo = bf16_rne(v - hi), the difference taken in fp32 (include/femasr_hip.h, w_bf16x3): float64 tensors holding
+    bf16 values."""
+    v = v.to(torch.float32)
+    hi = v.to(torch.bfloat16).to(torch.float32)
+    lo = (v - hi).to(torch.bfloat16).to(torch.float32)
+    return hi.to(torch.float64), lo.to(torch.float64)
+
+
+def bf16x3_model(x, w_oihw, bias, pos, res=(), drop=None):
+    """The documented arithmetic of the bf16x3 3x3 conv at the positions `pos`, written from its specification and not from the kernel:
+    activations and weights split into hi + lo (two bf16 values each); per 16-deep k-step three matrix products hi_x hi_w, hi_x lo_w,
+    lo_x hi_w (bf16 x bf16 is exact in fp32; the 16-term sums are taken exactly here) accumulated one after the other into an fp32
+    accumulator; K runs over 32-channel blocks, the 9 taps inside a block, two 16-deep steps inside a tap; then bias and residuals in
+    fp32.  drop: 'lo_x*hi_w' or 'hi_x*lo_w' leaves that product out (the mutations the bound must reject).  Returns (S, Cout) fp32."""
+    t, ok = R.gather_taps(x, pos, 3, 1, 1, False)                       # (S, 9, C)
+    t = t * ok[:, :, None]
+    S, _, C = t.shape
+    w = torch.as_tensor(np.asarray(w_oihw, np.float32), dtype=torch.float64)          # (O, C, 3, 3)
+    wk = w.permute(2, 3, 1, 0).reshape(9, C, w.shape[0])                              # [tap][c][o]
+    xh, xl = _bf16_split(t)
+    wh, wl = _bf16_split(wk)
+    terms = [(xh, wh), (xh, wl), (xl, wh)]
+    if drop == 'hi_x*lo_w':
+        terms.pop(1)
+    elif drop == 'lo_x*hi_w':
+        terms.pop(2)
+    else:
+        assert drop is None
+    acc = torch.zeros((S, w.shape[0]), dtype=torch.float32)
+    for q in range(C // 32):
+        for tap in range(9):
+            for s in range(2):
+                c0 = q * 32 + 16 * s
+                for (a, b) in terms:
+                    acc = (acc.to(torch.float64) + a[:, tap, c0:c0 + 16] @ b[tap, c0:c0 + 16]).to(torch.float32)
+    y = acc + torch.as_tensor(np.asarray(bias, np.float32))[None]
+    p = torch.as_tensor(pos)
+    for r in res:
+        y = y + r[p[:, 0], p[:, 1], p[:, 2]]
+    return y
+
+
+def _bf16x3_case(seed, cin, cout, silu):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((1, 12, 20, cin), generator=g)
+    if silu:          # what a GroupNorm + SiLU prologue hands the matrix cores: one-sided, most values near zero
+        x = torch.nn.functional.silu(x * 1.2 + 0.1)
+    w = torch.randn((cout, cin, 3, 3), generator=g) / math.sqrt(9 * cin)
+    b = (torch.rand(cout, generator=g) - 0.5) * 0.2
+    r1 = torch.randn((1, 12, 20, cout), generator=g)
+    return x, w, b, r1, R.conv_positions(1, 12, 20, seed)
+
+
+BF16X3_CAL = [(64, 64), (128, 128), (256, 256), (512, 128)]          # Cin, Cout (the network's decoder-side channel counts)
+
+
+def test_bf16x3_model_calibrates_its_constant():
+    """C_FORM['bf16x3'] >= 4x the worst c the model of the specified arithmetic needs (N(0,1) and SiLU-shaped inputs, Cin 64 .. 512)
+    and <= 208, the analytic worst case of the arithmetic (3 x 2^-18 relative for the two representation errors and the dropped
+    lo*lo term, + 16 for the fp32 accumulation): a larger constant would say nothing about the split."""
+    assert R.C_BF16X3_MAX == 3 * 2.0 ** -18 / R.U + 16.0 == 208.0
+    worst = {}
+    for i, (cin, cout) in enumerate(BF16X3_CAL):
+        for silu in (False, True):
+            x, w, b, r1, pos = _bf16x3_case(300 + i, cin, cout, silu)
+            ref, mag, pt, rest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, False, res=[r1])
+            c = _needed_c(bf16x3_model(x, w.numpy(), b.numpy(), pos, res=[r1]), ref, mag, pt, rest)
+            worst[(cin, 'silu' if silu else 'randn')] = c
+    print('\nbf16x3 model (worst c): ' + ', '.join(f'Cin {k[0]} {k[1]} {v:.3g}' for k, v in worst.items())
+          + f" (C_FORM {R.C_FORM['bf16x3']:g}, cap {R.C_BF16X3_MAX:g})")
+    assert R.C_FORM['bf16x3'] >= 4.0 * max(worst.values()), worst
+    assert R.C_FORM['bf16x3'] <= R.C_BF16X3_MAX
+
+
+@pytest.mark.parametrize('cin,cout', [(64, 64), (512, 128)])
+@pytest.mark.parametrize('drop', ['lo_x*hi_w', 'hi_x*lo_w'])
+@pytest.mark.parametrize('silu', [False, True], ids=['randn', 'silu'])
+def test_bf16x3_bound_rejects_a_missing_cross_term(cin, cout, drop, silu):
+    """The model's output passes the bf16x3 bound against the true fp64 reference; with either cross term left out it is rejected,
+    and most of its elements are over the bound one by one (not only the worst one)."""
+    x, w, b, r1, pos = _bf16x3_case(400 + cin, cin, cout, silu)
+    ref, mag, pt, rest = R.conv_ref(x, w.numpy(), b.numpy(), pos, 3, 1, 1, False, res=[r1])
+    bound = R.conv_bound(mag, pt, rest, 'bf16x3')
+    R.check(bf16x3_model(x, w.numpy(), b.numpy(), pos, res=[r1]), ref, bound, 'model')
+    bad = bf16x3_model(x, w.numpy(), b.numpy(), pos, res=[r1], drop=drop)
+    assert R.rejects(lambda: R.check(bad, ref, bound, drop)), drop
+    over = float(((bad.to(torch.float64) - ref).abs() > bound).double().mean())
+    assert over > 0.5, (drop, cin, over)
 
 
 def test_gn_bound_rejects_group_off_by_one():
@@ -173,34 +266,49 @@ CAL = [  # form, (B, H, W, Cin), Cout, oracle call
     ('split3x3', (1, 16, 24, 256), 256),
     ('split1x1', (1, 300, 1, 256), 768), ('split1x1', (1, 300, 1, 1024), 256),
     ('gemm_fp32', (2, 19, 23, 3), 256),
+    # linear_math 'fp32': the LDS-DMA GEMM (orc.linear) at the K and Cout of the network's 1x1 layers, a few hundred rows each
+    ('gemm_fp32', (1, 300, 1, 256), 768, dict(ksz=1)), ('gemm_fp32', (1, 333, 1, 256), 256, dict(ksz=1)),            # qkv, proj
+    ('gemm_fp32', (1, 300, 1, 256), 1024, dict(ksz=1, act=1)), ('gemm_fp32', (1, 270, 1, 1024), 256, dict(ksz=1)),   # fc1 + GELU, fc2
+    ('gemm_fp32', (1, 300, 1, 256), 512, dict(ksz=1)),                                                               # before_quant
+    # decoder_math 'fp32_direct' / linear_math 'fp32': the x2 convs as phase filters, the stride-2 encoder convs (conv_igemm)
+    ('direct', (1, 10, 12, 256), 128, dict(up2=True)), ('direct', (1, 9, 10, 128), 64, dict(up2=True)),
+    ('direct', (1, 24, 40, 64), 128, dict(stride=2)), ('direct', (1, 20, 24, 128), 256, dict(stride=2)),
 ]
 
 
 def test_calibration():
     from oracle import oracle as orc
     worst = {}
-    for i, (form, (B, H, W, cin), cout) in enumerate(CAL):
+    rows = []
+    for i, (form, (B, H, W, cin), cout, *opt) in enumerate(CAL):
+        opt = opt[0] if opt else {}
         rng = np.random.default_rng(100 + i)
-        ksz = 1 if form == 'split1x1' else (4 if form == 'gemm_fp32' else 3)
+        ksz = opt.get('ksz', 1 if form == 'split1x1' else (4 if form == 'gemm_fp32' else 3))
         pad = 0 if ksz == 1 else 1
-        up2 = form == 'wino_up2'
+        up2 = form == 'wino_up2' or opt.get('up2', False)
+        stride, act = opt.get('stride', 1), opt.get('act', 0)
         x = rng.standard_normal((B, H, W, cin)).astype(np.float32)
         w = (rng.standard_normal((cout, cin, ksz, ksz)) / math.sqrt(ksz * ksz * cin)).astype(np.float32)
         b = ((rng.random(cout) - 0.5) * 0.2).astype(np.float32)
         w_khwc = np.ascontiguousarray(w.transpose(2, 3, 1, 0))
         hv, wv = (2 * H, 2 * W) if up2 else (H, W)
-        ho, wo = hv + 2 * pad - ksz + 1, wv + 2 * pad - ksz + 1
+        ho, wo = (hv + 2 * pad - ksz) // stride + 1, (wv + 2 * pad - ksz) // stride + 1
         r1 = rng.standard_normal((B, ho, wo, cout)).astype(np.float32)
         if form == 'split3x3':
             y = orc.conv3x3_bf16s(x, w_khwc, b, r1, None, 1)
         elif form == 'split1x1':
             y = orc.linear_bf16s(x.reshape(-1, cin), w.reshape(cout, cin), b, 0, r1.reshape(-1, cout)).reshape(B, ho, wo, cout)
+        elif form == 'gemm_fp32' and ksz == 1:
+            y = orc.linear(x.reshape(-1, cin), np.ascontiguousarray(w.reshape(cout, cin).T), b, act, r1.reshape(-1, cout)).reshape(B, ho, wo, cout)
         else:
-            y = orc.conv2d(x, w_khwc, b, ksz, 1, pad, up2, 0, r1, None, wino=form in ('wino4', 'wino_up2'))
+            y = orc.conv2d(x, w_khwc, b, ksz, stride, pad, up2, act, r1, None, wino=form in ('wino4', 'wino_up2'))
         pos = R.conv_positions(B, ho, wo, i)
-        ref, mag, pt, rest = R.conv_ref(torch.as_tensor(x), w, b, pos, ksz, 1, pad, up2, res=[torch.as_tensor(r1)])
+        ref, mag, pt, rest = R.conv_ref(torch.as_tensor(x), w, b, pos, ksz, stride, pad, up2, res=[torch.as_tensor(r1)], act=act)
         got = torch.as_tensor(y[pos[:, 0], pos[:, 1], pos[:, 2]])
-        worst[form] = max(worst.get(form, 0.0), _needed_c(got, ref, mag, pt, rest))
+        c = _needed_c(got, ref, mag, pt, rest)
+        rows.append(f"  {form:10s} {cin:4d}->{cout:4d} k{ksz}s{stride}{' x2' if up2 else ''}{' gelu' if act else ''}: {c:.3g}")
+        worst[form] = max(worst.get(form, 0.0), c)
+    print('\ncalibration rows (the c each case needs):\n' + '\n'.join(rows))
     print('\ncalibration (worst c per form): ' + ', '.join(f'{k} {v:.3g} (C_FORM {R.C_FORM[k]:g})' for k, v in worst.items()))
     for k, v in worst.items():
         assert R.C_FORM[k] >= 4.0 * v, (k, v, R.C_FORM[k])
@@ -379,3 +487,139 @@ def test_halo_kernels_leave_at_2_to_31_input_elements():
     assert lib.femasr_conv2d(None, ctypes.byref(a)) != 0 and b'bf16x3' in lib.femasr_last_error()
     a.B = 7
     _lib.check(lib.femasr_debug_conv_variant_name(ctypes.byref(a), buf, len(buf)))      # eligible below the limit
+
+
+# ---------------------------------------------------------------- the inventories of the non-default modes
+BF16X3_REACHABLE = [          # typed in: g_v16 rows 0-2, 6-11, 15-17 of kernels_conv_bf16.hip (what femasr_conv_bf16x3_pick_variant returns)
+    'conv3x3_halo_bf16x3<8x16x128,FEMASR_PRO_NONE,up2=false,waves=2x2>',
+    'conv3x3_halo_bf16x3<8x16x128,FEMASR_PRO_GN_SILU,up2=false,waves=2x2>',
+    'conv3x3_halo_bf16x3<8x16x128,FEMASR_PRO_NONE,up2=true,waves=2x2>',
+    'conv3x3_halo_bf16x3<8x16x32,FEMASR_PRO_NONE,up2=false,waves=4x1>',
+    'conv3x3_halo_bf16x3<8x16x32,FEMASR_PRO_GN_SILU,up2=false,waves=4x1>',
+    'conv3x3_halo_bf16x3<8x16x32,FEMASR_PRO_NONE,up2=true,waves=4x1>',
+    'conv3x3_halo_bf16x3<8x16x256,FEMASR_PRO_NONE,up2=false,waves=1x4>',
+    'conv3x3_halo_bf16x3<8x16x256,FEMASR_PRO_GN_SILU,up2=false,waves=1x4>',
+    'conv3x3_halo_bf16x3<8x16x256,FEMASR_PRO_NONE,up2=true,waves=1x4>',
+    'conv3x3_halo_bf16x3<8x16x64,FEMASR_PRO_NONE,up2=false,waves=2x2>',
+    'conv3x3_halo_bf16x3<8x16x64,FEMASR_PRO_GN_SILU,up2=false,waves=2x2>',
+    'conv3x3_halo_bf16x3<8x16x64,FEMASR_PRO_NONE,up2=true,waves=2x2>',
+]
+
+
+def _mode_cases(dm, lm):
+    """Every case tests/test_gpu_mode_anchor.py launches for one mode: bench workloads + product shapes (before de-duplication)."""
+    import anchor_cases as A
+    out = {}
+    for wl in R.WORKLOADS:
+        out.update(A.inventory(wl, modes=(dm,), linear_math=lm, split_res2=True)[0])
+    for n, subs in A.MODE_PRODUCT.items():
+        out.update(A.inventory(n, modes=(dm,), linear_math=lm, sub_batches=subs, split_res2=True)[0])
+    return out
+
+
+def test_bf16x3_inventory_puts_every_conv_behind_the_lookup_on_the_matrix_cores():
+    import anchor_cases as A
+    for wl in R.WORKLOADS:
+        convs, _ = A.inventory(wl, modes=('bf16x3',))
+        behind = [c for c in convs.values() if c['L']['behind']]
+        assert len(behind) >= 20
+        for c in behind:
+            if c['L']['key'] == 'out_conv':
+                assert c['form'] == 'direct' and c['slot'].startswith('conv3x3_cout3<'), c['slot']
+            else:
+                assert c['form'] == 'bf16x3' and c['slot'].startswith('conv3x3_halo_bf16x3<'), (c['L']['key'], c['form'], c['slot'])
+                assert c['slot'] in BF16X3_REACHABLE
+        for c in convs.values():          # in front of the lookup nothing changes with decoder_math
+            assert c['L']['behind'] or c['form'] != 'bf16x3'
+    # beyond the kernel's size limit the planner's choice is the direct form (64-bit generic kernel): 2 x 4096^2 x 64 is exactly 2^31
+    L = dict(B=2, H=4096, W=4096, cin=64, cout=64, ksz=3, stride=1, pad=1, up2=False, pro=True, act=0, behind=True)
+    assert R.conv_form(L, 'bf16x3', 'bf16_split') == 'direct' and R.conv_form(dict(L, H=4094), 'bf16x3', 'bf16_split') == 'bf16x3'
+    assert R.conv_form(dict(L, B=1, H=2048, W=2048, cin=128, up2=True, pro=False), 'bf16x3', 'bf16_split') == 'bf16x3'      # 2^29 in, 2^30 out
+    assert R.conv_form(dict(L, B=2, H=2048, W=2048, cin=128, up2=True, pro=False), 'bf16x3', 'bf16_split') == 'direct'      # 2^31 out
+    assert R.conv_form(dict(L, up2=True, B=1, H=64, W=64), 'bf16x3', 'bf16_split') == 'direct'                               # prologue with x2
+
+
+def test_bf16x3_instantiations_are_all_launched():
+    """Each of the 12 reachable instantiations has a case in what the mode module launches: in a bench or product inventory, or - for
+    the ones no listed workload reaches - among anchor_cases.bf16x3_unit_cases(), which hold exactly those."""
+    import anchor_cases as A
+    assert len(set(BF16X3_REACHABLE)) == 12
+    reached = {c['slot'] for c in _mode_cases('bf16x3', 'bf16_split').values() if c['form'] == 'bf16x3'}
+    assert reached <= set(BF16X3_REACHABLE)
+    unit = {c['slot'] for c in A.bf16x3_unit_cases()}
+    missing = [n for n in BF16X3_REACHABLE if n not in reached | unit]
+    print('\nbf16x3 instantiations no listed workload reaches (unit shapes): ' + ', '.join(sorted(set(BF16X3_REACHABLE) - reached)))
+    assert not missing, f'no listed workload and no unit shape reaches: {missing}'
+    assert unit == set(BF16X3_REACHABLE) - reached, 'the unit shapes are for the instantiations no workload reaches, and only those'
+    assert len(reached) == 7
+
+
+def test_direct_and_fp32_linear_inventories_hold_no_other_form():
+    import anchor_cases as A
+    direct = _mode_cases('fp32_direct', 'bf16_split')
+    assert direct and not [c['slot'] for c in direct.values() if c['form'].startswith('wino') or c['form'] == 'bf16x3']
+    assert any(c['L']['up2'] and 'up2=true' in c['slot'] and c['slot'].startswith('conv3x3_halo<') for c in direct.values())   # phase filters
+    assert any(c['L']['nres'] == 2 and c['L']['pro'] and c['slot'].startswith('conv3x3_halo<') for c in direct.values())
+    lin = _mode_cases('fp32', 'fp32')
+    assert lin and not [c['slot'] for c in lin.values() if c['form'].startswith('split')]
+    gemm = [c for c in lin.values() if R.gemm_fp32_layer(c['L'])]
+    assert {(c['L']['cin'], c['L']['cout']) for c in gemm} >= {(256, 768), (256, 256), (256, 1024), (1024, 256), (256, 512)}
+    assert all(c['slot'].startswith('gemm_dma<') for c in gemm), sorted({c['slot'] for c in gemm})
+    assert max(c['L']['H'] for c in gemm) == 16 * 144 * 144 == 331776          # the CLI's 16 windows (82 944 rows and up at the bench's sub-batches)
+    assert any(c['L']['stride'] == 2 and c['slot'].startswith('conv_igemm<') for c in lin.values())
+    assert any(c['L']['act'] == 1 for c in gemm)
+
+
+def test_skip_schedule_follows_the_mode():
+    """run_tail: the encoder skip of decoder stage i + 1 is the in_add of that stage's x2 conv when the conv is in the wino_up2 form,
+    otherwise the second residual of stage i's last conv.  LQ workloads: every decoder stage but the last hands a skip to the next;
+    HQ: no skips.  (The slot names of the halo, bf16x3 and GEMM kernels do not tell the residual count, so the profile-slot coverage
+    test on the GPU cannot see this schedule: this host test, written from model.hip run_tail, is what holds it.)"""
+    import anchor_cases as A
+    for wl_name, wl in R.WORKLOADS.items():
+        sub_b = R.sub_batches(wl['batch'], R.BENCH_STREAMS)[0]
+        by_mode = {dm: {l['key']: l for l in A._layers(wl_name, sub_b, dm) if l['kind'] == 'conv'} for dm in ('fp32', 'fp32_strict', 'fp32_direct', 'bf16x3')}
+        assert by_mode['fp32'] == by_mode['fp32_strict'] and by_mode['fp32_direct'] == by_mode['bf16x3']
+        wino, direct = by_mode['fp32'], by_mode['fp32_direct']
+        assert list(wino) == list(direct)
+        diff = sorted(k for k in wino if wino[k] != direct[k])
+        depth = sum(1 for k in wino if k.startswith('decoder_group.') and k.endswith('.block.1'))
+        if not wl['cfg']['LQ_stage']:
+            assert not diff and not any(l['in_add'] or l['nres'] == 2 for l in wino.values())
+            continue
+        want = sorted([f'decoder_group.{i}.block.3.conv.5' for i in range(depth - 1)] + [f'decoder_group.{i + 1}.block.1' for i in range(depth - 1)])
+        assert diff == want, (wl_name, diff)
+        for i in range(depth - 1):
+            a, b = f'decoder_group.{i}.block.3.conv.5', f'decoder_group.{i + 1}.block.1'
+            assert (wino[a]['nres'], wino[b]['in_add']) == (1, True) and (direct[a]['nres'], direct[b]['in_add']) == (2, False)
+            assert {k: v for k, v in wino[a].items() if k != 'nres'} == {k: v for k, v in direct[a].items() if k != 'nres'}
+        assert not any(l['in_add'] for l in direct.values())
+    # the schedule follows the FORM, not the mode's name: past the Winograd limit the default mode folds the skip into res2 as well
+    big = {l['key']: l for l in A._layers('whole599x599_x4', 1, 'fp32') if l['kind'] == 'conv'}
+    assert big['decoder_group.1.block.3.conv.5']['nres'] == 2 and not big['decoder_group.2.block.1']['in_add']
+
+
+def test_mode_inventory_adds_only_what_the_default_inventories_lack():
+    import anchor_cases as A
+    default = set()
+    for wl in R.WORKLOADS:
+        default |= set(A.inventory(wl)[0])
+    n = {}
+    for dm, lm in A.MODES:
+        convs, small = A.mode_inventory(list(R.WORKLOADS), dm, lm)
+        assert convs and not set(convs) & default
+        assert not small          # (workload_layers lists the moments pass of every GroupNorm in every mode: the default inventories hold them)
+        assert not A.mode_inventory(dict(A.MODE_PRODUCT), dm, lm)[1]
+        n[dm, lm] = len(convs)
+        prod, _ = A.mode_inventory(dict(A.MODE_PRODUCT), dm, lm)
+        assert prod and not set(prod) & (default | set(A.product_inventory(dict(A.MODE_PRODUCT))[0]))
+        if lm == 'bf16_split':          # the 16-window launches behind the lookup: 5.4 GB tensors, past 2^32 bytes
+            assert any(4 * c['L']['B'] * c['L']['H'] * c['L']['W'] * c['L']['cin'] > 2 ** 32 for c in prod.values())
+        else:                           # the Swin layers at 16 windows: 331 776 rows
+            assert any(c['L']['H'] == 331776 and c['L']['cin'] == 1024 for c in prod.values())
+        res2 = [c for k, c in {**convs, **prod}.items() if c['L']['nres'] == 2]
+        assert res2 and all(k[-1] == 'res2' for k, c in {**convs, **prod}.items() if c['L']['nres'] == 2)
+    print('\nmode inventories (bench shapes, new cases): ' + ', '.join(f'{k[0]}/{k[1]} {v}' for k, v in n.items()))
+    # gemm_fp32_layer cases take the constant calibrated for the LDS-DMA GEMM
+    lin, _ = A.mode_inventory(list(R.WORKLOADS), 'fp32', 'fp32')
+    assert any(R.gemm_fp32_layer(c['L']) and c['form'] == 'direct' for c in lin.values())

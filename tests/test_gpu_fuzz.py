@@ -75,6 +75,9 @@ def test_fuzz_conv3x3_bf16x3_within_tolerance(cuda_device, c):
         got, part = got
     scale = max(1.0, float(np.abs(ref).max()))
     assert got.shape == ref.shape and float(np.abs(got - ref).max()) <= 1e-4 * scale
+    # every element within the per-element fp64 bound of the form (tests/fp64_ref.py): ragged Cout, odd sizes, 0 / 1 / 2 residuals
+    import fp64_ref as R
+    R.check_whole_conv3x3(x, w, bias, got, 'bf16x3', up2=up, pro=(a_, b_) if c['gn'] else None, res=[r1, r2], what=repr(c))
     if part is not None:                      # fused GroupNorm partial moments of the output
         assert not torch.isnan(part).any()
         g2 = synth.uniform(9, 'bzg2', (c['cout'],), 0.5, 1.5)
