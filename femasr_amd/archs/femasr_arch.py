@@ -231,9 +231,12 @@ class FeMaSRNet(nn.Module):
         # True: each (shape, mode) class is captured once into a hipGraph (torch.cuda.CUDAGraph around femasr_forward, which
         # is capture-safe: no allocation / synchronisation inside) and replayed; inputs are copied into the graph's static
         # buffer and the outputs are copies of its static outputs.  Only pays when the ~330 launches are host-bound (tiny
-        # batches); results are bit-identical.
+        # batches); results are bit-identical (images and every index map: tests/test_gpu_graph_streams.py).  A cached graph
+        # stays valid across weight changes (the handle repacks into the SAME allocations, see _release) and is dropped by
+        # invalidate_weights(), by a new native handle and by the cache bound in _run.  Not with enable_profile(True): _run refuses.
         self.use_graph = False
         self._graphs = {}
+        self._profile_on = False        # what enable_profile() last set on the live handle (a new handle starts with it off)
         self.debug_wino_limits = None   # tests only: (log2_total, log2_image) for this net's planner (include/femasr_hip_debug.h)
 
     # ------------------------------------------------------------------ weight change tracking
@@ -279,6 +282,7 @@ class FeMaSRNet(nn.Module):
             _lib.check(lib.femasr_create(ctypes.byref(cfg), ctypes.byref(h)))
             self._handle, self._handle_device, self._pushed = h, dev_index, {}
             self._weights_dirty = True
+            self._profile_on = False
         # the walk over the (~480-tensor) state dict only runs when something may have changed; otherwise a cheap scan of
         # the parameters' version counters (in-place updates) decides
         if not self._weights_dirty:
@@ -328,7 +332,12 @@ class FeMaSRNet(nn.Module):
 
     def _release(self):
         if getattr(self, '_handle', None) is not None:
-            self._graphs = {}             # captured graphs bake pointers into the handle's repacked weights / plans: drop them with it
+            # Captured graphs bake pointers into the handle's repacked weights: drop them with it.  They are NOT dropped when
+            # weights change (load_state_dict, .to(), in-place updates): femasr_set_weight / femasr_finalize_weights repack into
+            # the allocations made at the first push - repacked weight buffers are never reallocated while a handle lives - so a
+            # replay reads the new weights.  tests/test_gpu_graph_streams.py::test_weights_changed_under_a_live_graph holds that
+            # invariant: a launcher that frees and reallocates has to clear `_graphs` wherever `_weights_dirty` leads to a push.
+            self._graphs = {}
             _lib.load().femasr_destroy(self._handle)
             self._handle = None
 
@@ -355,6 +364,7 @@ class FeMaSRNet(nn.Module):
         lib, h = self._native(next(self.parameters()).device)
         _lib.check(lib.femasr_profile_enable(h, int(on)))
         _lib.check(lib.femasr_profile_reset(h))
+        self._profile_on = bool(on)
 
     def profile(self):
         """{kernel name: (ms, launches, flops, bytes)} since the last reset (HIP events on the launch stream)."""
@@ -373,22 +383,31 @@ class FeMaSRNet(nn.Module):
         tensor (`out`, when given, is validated and written in place).  `flags`: the native arguments in front of `pad_mode`
         (`femasr_forward_u8`'s bgr).  Returns (out, all VQ indices as one flat tensor or None, workspace, [(qh, qw)] per codebook)."""
         b, _, hh, ww = fmt.bchw(x)
-        oh, ow, nq = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        qh, qw = (ctypes.c_int * _lib.MAX_CODEBOOKS)(), (ctypes.c_int * _lib.MAX_CODEBOOKS)()
-        _lib.check(lib.femasr_forward_shapes(h, hh, ww, pad_mode, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(nq),
-                                             ctypes.byref(qh), ctypes.byref(qw)))
-        qhw = [(qh[k], qw[k]) for k in range(nq.value)]
+        shape, qhw = self._geometry(lib, h, fmt, b, hh, ww, pad_mode)
         ws = self._workspace(lib.femasr_workspace_bytes, h, (b, hh, ww, pad_mode), x.device)
-        shape = tiling.tile_shape(fmt.dtype, b, 3, oh.value, ow.value)
         if out is None:
             out = torch.empty(shape, dtype=fmt.dtype, device=x.device)
-        elif tuple(out.shape) != shape or out.dtype != fmt.dtype or out.device != x.device or not out.is_contiguous():
-            raise ValueError(f'out= must be a contiguous {fmt.dtype} tensor of shape {shape} on {x.device}, got '
-                             f'{tuple(out.shape)} {out.dtype} on {out.device}')
+        else:
+            self._check_out(out, shape, fmt.dtype, x.device)
         idx_all = torch.empty((sum(b * a * c for a, c in qhw),), dtype=torch.int64, device=x.device) if indices else None
         _lib.check(getattr(lib, fmt.forward)(h, self._stream(x.device), _lib.ptr(x), b, hh, ww, *flags, pad_mode, _lib.ptr(out),
                                              None if idx_all is None else _lib.ptr(idx_all), _lib.ptr(ws), ws.numel()))
         return out, idx_all, ws, qhw
+
+    @staticmethod
+    def _geometry(lib, h, fmt, b, hh, ww, pad_mode):
+        """(shape of the result tensor in the format's layout, [(qh, qw)] per codebook) of a forward on b images of hh x ww."""
+        oh, ow, nq = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        qh, qw = (ctypes.c_int * _lib.MAX_CODEBOOKS)(), (ctypes.c_int * _lib.MAX_CODEBOOKS)()
+        _lib.check(lib.femasr_forward_shapes(h, hh, ww, pad_mode, ctypes.byref(oh), ctypes.byref(ow), ctypes.byref(nq),
+                                             ctypes.byref(qh), ctypes.byref(qw)))
+        return tiling.tile_shape(fmt.dtype, b, 3, oh.value, ow.value), [(qh[k], qw[k]) for k in range(nq.value)]
+
+    @staticmethod
+    def _check_out(out, shape, dtype, device):
+        if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+            raise ValueError(f'out= must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got '
+                             f'{tuple(out.shape)} {out.dtype} on {out.device}')
 
     def _run(self, x, pad_mode, out=None):
         if x.dim() != 4 or x.shape[1] != self.in_channel:
@@ -397,6 +416,13 @@ class FeMaSRNet(nn.Module):
         x = x.detach().to(torch.float32).contiguous()
         b, _, hh, ww = x.shape
         if self.use_graph:
+            if self._profile_on:
+                # the profiler's event pairs would be recorded INTO the capture and never on a stream: profile() would then wait
+                # on events that no replay ever signals.  Refused here, before anything is captured.
+                raise _lib.FemasrError('use_graph = True cannot be combined with enable_profile(True): per-kernel events cannot be '
+                                       'read back from a replayed hipGraph; call enable_profile(False) or set use_graph = False')
+            if out is not None:                                                      # (as the eager call: refused before any launch or capture)
+                self._check_out(out, self._geometry(lib, h, _FP32, b, hh, ww, pad_mode)[0], _FP32.dtype, x.device)
             key = (b, hh, ww, pad_mode, self.num_streams, self.decoder_math, self.linear_math, x.device.index)
             ent = self._graphs.get(key)
             if ent is None:

@@ -111,15 +111,16 @@ class _MemoOracle:
         return call
 
 
-def oracle_net(cfg_name, weights, linear_math='bf16_split'):
-    """linear_math: arithmetic of the 1x1 / Linear layers - 'bf16_split' = the product default (FeMaSRNet.linear_math),
+def oracle_net(cfg_name, weights, linear_math='bf16_split', winograd=True):
+    """winograd=False: every conv in the direct form, the arithmetic of FeMaSRNet(decoder_math='fp32_direct').
+    linear_math: arithmetic of the 1x1 / Linear layers - 'bf16_split' = the product default (FeMaSRNet.linear_math),
     'fp32' = the fp32 fmaf chain (FeMaSRNet(linear_math='fp32')); the CPU-only golden tests run their large cases in 'fp32'
     (the restated matrix-instruction arithmetic costs ~30x the fmaf chain on a CPU)."""
     from oracle import oracle as orc
     cfg = CONFIGS[cfg_name] if isinstance(cfg_name, str) else cfg_name
     net = orc.OracleNet(weights, codebook_params=cfg['codebook_params'], LQ_stage=cfg['LQ_stage'], scale_factor=cfg.get('scale_factor', 4),
-                        linear_math=linear_math)
-    return _MemoOracle(net, (_fingerprint(weights), repr(sorted((k, repr(v)) for k, v in cfg.items())), linear_math))
+                        linear_math=linear_math, winograd=winograd)
+    return _MemoOracle(net, (_fingerprint(weights), repr(sorted((k, repr(v)) for k, v in cfg.items())), linear_math, winograd))
 
 
 def golden_cfg(g):
