@@ -42,7 +42,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 104      # femasr_version(): the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
+ABI_VERSION = 105      # femasr_version(): femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -127,6 +127,11 @@ SIGNATURES = {
     'femasr_psnr_ssim_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
     'femasr_psnr_ssim': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp, vp, szt]),
     'femasr_ssim_window': (c_int, [ctypes.POINTER(ctypes.c_double)]),
+    'femasr_imresize_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_imresize': (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, szt]),
+    'femasr_niqe_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_niqe_plane_offsets': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(szt * 4)]),
+    'femasr_niqe_features': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, c_int, vp, vp, vp, szt]),
     'femasr_clock_probe': (c_int, [vp, c_int, vp]),
     'femasr_clock_probe_entries': (c_int, []),
 }

@@ -18,8 +18,12 @@ definitions (crop_border, test_y_channel on the BT.601 Y of the uint8-rounded im
 uint8 SR and GT images already on the device, within 1e-9 dB / 1e-12 of these functions.  'lpips' (AlexNet) and 'lpips-vgg'
 (VGG16) are LPIPS v0.1 on the GPU (femasr_amd.lpips, csrc/lpips.hip) when their options carry `pretrained_model_path`
 (pyiqa's keyword; optionally `backbone_model_path`): scored on (sr_u8 / 255, gt) as femasr_model.py:262 does, the uint8 SR
-image never leaving the device.  Without a weight file (weights are never downloaded) they, like every other type (niqe,
-musiq, ...), are reported as skipped (None).  There is no CPU path: the module needs a GPU and the HIP library.
+image never leaving the device.  'niqe' is the no-reference NIQE (BasicSR's calculate_niqe, restated below as calculate_niqe with its
+pieces: _niqe_y, _convolve_nearest, imresize / imresize_tables, aggd_tables, niqe_features, niqe_score_from_features) when its options
+carry `pretrained_model_path` (a local niqe_pris_params.npz): scored on sr_u8 on the GPU (femasr_amd.niqe, csrc/niqe.hip) for every image,
+also of a dataset without ground truth; only its tail (36 numbers per block) runs on the host, in the definition's own function.  Without
+a weight / parameter file (none is ever downloaded) these types, like every other type (musiq, ...), are reported as skipped (None).
+There is no CPU path: the module needs a GPU and the HIP library.
 """
 import logging
 import os
@@ -31,6 +35,7 @@ import torch
 
 from .. import imgproc
 from .. import lpips as lpips_metric
+from .. import niqe as niqe_metric
 from .. import psnr_ssim
 from ..archs import build_network
 from . import MODEL_REGISTRY
@@ -89,6 +94,197 @@ def calculate_ssim(img, img2, crop_border=0, test_y_channel=False, **_):
 
 
 _METRICS = {'psnr': calculate_psnr, 'ssim': calculate_ssim}
+
+
+# ---------------------------------------------------------------- imresize and NIQE: the definitions (numpy, fp64)
+def _cubic(x):
+    """matlab_functions.py:6-13."""
+    ax = np.abs(x)
+    ax2, ax3 = ax * ax, ax * ax * ax
+    return (1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1) + (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((ax > 1) & (ax <= 2))
+
+
+def imresize_tables(in_length, out_length, scale, antialiasing=True):
+    """calculate_weights_indices (matlab_functions.py:16-82) in fp64: (weights (out_length, taps) float64, rows (out_length, taps) int32).
+    The reference pads the image symmetrically; here the padding is folded into the indices: a 1-based index i < 1 reads 1 - i, i > n reads
+    2n + 1 - i, and `rows` holds them 0-based.  Raises ValueError where a reflected index leaves the image (the reference raises there too).
+    The column trimming is the reference's: the first (last) column goes when ANY of its weights is exactly zero."""
+    import math
+    if not (in_length >= 1 and out_length >= 1 and scale > 0):
+        raise ValueError(f'imresize: length {in_length} -> {out_length} at scale {scale}')
+    kernel_width = 4.0
+    aa = scale < 1 and antialiasing
+    if aa:
+        kernel_width = kernel_width / scale
+    x = np.arange(1, out_length + 1, dtype=np.float64)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = np.floor(u - kernel_width / 2)
+    p = math.ceil(kernel_width) + 2
+    ind = left[:, None] + np.arange(p, dtype=np.float64)[None, :]
+    dist = u[:, None] - ind
+    w = scale * _cubic(dist * scale) if aa else _cubic(dist)
+    total = np.zeros(out_length)
+    for k in range(p):                  # the row sums in ascending order
+        total = total + w[:, k]
+    w = w / total[:, None]
+    zeros = (w == 0).sum(0)
+    if zeros[0] != 0:
+        ind, w = ind[:, 1:p - 1], w[:, 1:p - 1]
+    if zeros[-1] != 0:
+        ind, w = ind[:, :p - 2], w[:, :p - 2]
+    i = ind.astype(np.int64)
+    i = np.where(i < 1, 1 - i, i)
+    i = np.where(i > in_length, 2 * in_length + 1 - i, i)
+    if i.min() < 1 or i.max() > in_length:
+        raise ValueError(f'imresize: a length of {in_length} is too short for scale {scale}'
+                         f'{" with antialiasing" if aa else ""}: the symmetric padding would leave the image')
+    return np.ascontiguousarray(w), np.ascontiguousarray(i - 1, dtype=np.int32)
+
+
+def imresize(img, scale, antialiasing=True):
+    """MATLAB-style bicubic imresize (matlab_functions.py:86-178) of (..., H, W) planes in fp64: the H pass, then the W pass; every output
+    is one accumulator over its taps in ascending order from 0.0.  Output size ceil(n * scale)."""
+    import math
+    img = np.asarray(img, dtype=np.float64)
+    h, w = img.shape[-2:]
+    oh, ow = math.ceil(h * scale), math.ceil(w * scale)
+    wh, ih = imresize_tables(h, oh, scale, antialiasing)
+    ww, iw = imresize_tables(w, ow, scale, antialiasing)
+    out1 = np.zeros(img.shape[:-2] + (oh, w))
+    for k in range(wh.shape[1]):
+        out1 = out1 + wh[:, k][:, None] * img[..., ih[:, k], :]
+    out2 = np.zeros(img.shape[:-2] + (oh, ow))
+    for k in range(ww.shape[1]):
+        out2 = out2 + ww[:, k] * out1[..., :, iw[:, k]]
+    return out2
+
+
+def _niqe_y(img_u8_rgb):
+    """The rounded BT.601 luma NIQE scores, as ONE fixed-order fp64 expression (no BLAS, unlike _to_y): on the 194 RGB triples whose exact Y
+    is k + 0.5 one ulp decides the rounded pixel."""
+    x = img_u8_rgb.astype(np.float64)
+    return np.round(((65.481 * x[..., 0] + 128.553 * x[..., 1]) + 24.966 * x[..., 2]) / 255.0 + 16.0)
+
+
+def _convolve_nearest(x, window):
+    """scipy.ndimage.convolve(x, window, mode='nearest') for an odd square window, restated: the raster walk over the FLIPPED window, one
+    accumulator from 0.0, no fma.  Equal to scipy bit for bit (tests/test_niqe_host.py); in flat regions x - mu is rounding noise whose sign
+    decides which pixels count as negative, so the order is part of the definition."""
+    k = window.shape[0]
+    r = k // 2
+    wf = window[::-1, ::-1]
+    xp = np.pad(x, r, mode='edge')
+    h, w = x.shape
+    s = np.zeros((h, w))
+    for a in range(k):
+        for b in range(k):
+            s = s + wf[a, b] * xp[a:a + h, b:b + w]
+    return s
+
+
+_AGGD_TABLES = None
+
+
+def aggd_tables():
+    """(r_gam, gamma(1/gam), gamma(2/gam), gamma(3/gam), gam), gam = arange(0.2, 10.001, 0.001) (9801 values): the grid of the AGGD shape
+    search, shared by the definition and the GPU path (which has no gamma function).  math.gamma, not scipy.special.gamma."""
+    global _AGGD_TABLES
+    if _AGGD_TABLES is None:
+        import math
+        gam = np.arange(0.2, 10.001, 0.001)
+        rec = np.reciprocal(gam)
+        g1 = np.array([math.gamma(v) for v in rec])
+        g2 = np.array([math.gamma(v) for v in rec * 2])
+        g3 = np.array([math.gamma(v) for v in rec * 3])
+        _AGGD_TABLES = (g2 * g2 / (g1 * g3), g1, g2, g3, gam)
+    return _AGGD_TABLES
+
+
+def _aggd(x):
+    """Asymmetric generalised Gaussian fit of one map: (grid position, alpha, beta_l, beta_r, margin); margin is the gap between the best and
+    the second-best |r_gam - rn| (NaN when rn is).  An empty side has mean NaN, and argmin of an all-NaN objective is 0: alpha 0.2, that side's beta NaN."""
+    r_gam, g1, _, g3, gam = aggd_tables()
+    x = x.ravel()
+    with np.errstate(all='ignore'):
+        neg, pos = x[x < 0], x[x > 0]
+        l = np.sqrt(np.float64(np.sum(neg * neg)) / np.float64(neg.size))
+        r = np.sqrt(np.float64(np.sum(pos * pos)) / np.float64(pos.size))
+        g = l / r
+        rhat = np.mean(np.abs(x)) ** 2 / np.mean(x * x)
+        rn = rhat * (g * g * g + 1) * (g + 1) / ((g * g + 1) * (g * g + 1))
+        d = r_gam - rn
+        p = int(np.argmin(d * d))
+        two = np.partition(np.abs(d), 1)[:2]
+        k = np.sqrt(g1[p] / g3[p])
+        return p, gam[p], l * k, r * k, float(two[1] - two[0])
+
+
+def _niqe_block_feature(block):
+    """18 features of one block at one scale, the 5 grid positions and the smallest margin."""
+    _, g1, g2, _, _ = aggd_tables()
+    p, alpha, bl, br, margin = _aggd(block)
+    feat, poss, margins = [alpha, (bl + br) / 2], [p], [margin]
+    for shift in ([0, 1], [1, 0], [1, 1], [1, -1]):
+        p, alpha, bl, br, margin = _aggd(block * np.roll(block, shift, axis=(0, 1)))          # circular inside the block
+        feat += [alpha, (br - bl) * (g2[p] / g1[p]), bl, br]
+        poss.append(p)
+        margins.append(margin)
+    return feat, poss, margins
+
+
+def niqe_features(y, window, details=None):
+    """(features (n_blocks, 36), alpha grid positions (n_blocks, 10)) of a rounded luma plane.  Blocks of 96 x 96 (48 x 48 at the second
+    scale) in the order `for iw: for ih`.  `details`, a dict, receives the planes y, z, y2, z2 and the alpha margins (n_blocks, 10)."""
+    window = np.asarray(window, dtype=np.float64)
+    nh, nw = y.shape[0] // 96, y.shape[1] // 96
+    if nh < 1 or nw < 1:
+        raise ValueError(f'niqe: a plane of {y.shape[0]}x{y.shape[1]} holds no 96x96 block')
+    y = np.ascontiguousarray(y[:nh * 96, :nw * 96], dtype=np.float64)
+    feats, poss, margins = [], [], []
+    for scale in (1, 2):
+        mu = _convolve_nearest(y, window)
+        sigma = np.sqrt(np.abs(_convolve_nearest(y * y, window) - mu * mu))
+        z = (y - mu) / (sigma + 1)
+        if details is not None:
+            details['y' if scale == 1 else 'y2'], details['z' if scale == 1 else 'z2'] = y, z
+        n = 96 // scale
+        rows = [_niqe_block_feature(z[ih * n:(ih + 1) * n, iw * n:(iw + 1) * n]) for iw in range(nw) for ih in range(nh)]
+        feats.append(np.array([r[0] for r in rows]))
+        poss.append(np.array([r[1] for r in rows]))
+        margins.append(np.array([r[2] for r in rows]))
+        if scale == 1:
+            y = imresize(y / 255.0, 0.5, antialiasing=True) * 255.0        # not rounded
+    if details is not None:
+        details['margin'] = np.concatenate(margins, 1)
+    return np.concatenate(feats, 1), np.concatenate(poss, 1).astype(np.int32)
+
+
+def niqe_score_from_features(features, mu_pris, cov_pris):
+    """NIQE's tail on the (n_blocks, 36) features, shared by the definition and the GPU path: nanmean, the covariance of the rows without
+    NaN, pinv of the pooled covariance, the quadratic form.  Fewer than two rows without NaN leave the covariance undefined: NaN."""
+    import warnings
+    d = np.asarray(features, dtype=np.float64).reshape(-1, 36)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', category=RuntimeWarning)
+        mu_d = np.nanmean(d, axis=0)
+    dn = d[~np.isnan(d).any(axis=1)]
+    if dn.shape[0] < 2:
+        return float('nan')
+    pooled = (np.asarray(cov_pris, dtype=np.float64).reshape(36, 36) + np.cov(dn, rowvar=False)) / 2
+    diff = np.asarray(mu_pris, dtype=np.float64).reshape(36) - mu_d
+    if not (np.isfinite(pooled).all() and np.isfinite(diff).all()):
+        return float('nan')
+    return float(np.sqrt(diff @ np.linalg.pinv(pooled) @ diff))
+
+
+def calculate_niqe(img, crop_border, params, **_):
+    """BasicSR's calculate_niqe(img, crop_border, input_order='HWC', convert_to='y') for a uint8 RGB image; params = (mu_pris_param,
+    cov_pris_param, gaussian_window) as femasr_amd.niqe.load_pris_params returns them."""
+    mu_pris, cov_pris, window = params
+    y = _niqe_y(img)
+    if crop_border:
+        y = y[crop_border:-crop_border, crop_border:-crop_border]
+    return niqe_score_from_features(niqe_features(y, window)[0], mu_pris, cov_pris)
 
 
 @MODEL_REGISTRY.register()
@@ -177,10 +373,15 @@ class FeMaSRModel:
         # psnr / ssim on the device; the CPU functions in _METRICS are their definition
         pixel_metrics = {name: psnr_ssim.create_metric(m['type'], **{k: v for k, v in m.items() if k not in ('type', 'better')})
                          for name, m in metrics.items() if m.get('type') in _METRICS}
-        skipped = sorted(name for name, m in metrics.items() if m.get('type') not in _METRICS and name not in gpu_metrics)
+        # niqe needs no ground truth: scored on the device for every image, also of a dataset without `gt`
+        noref_metrics = {name: niqe_metric.create_metric('niqe', **{k: v for k, v in m.items() if k not in ('type', 'better')})
+                         for name, m in metrics.items() if m.get('type') == 'niqe' and m.get('pretrained_model_path')}
+        skipped = sorted(name for name, m in metrics.items()
+                         if m.get('type') not in _METRICS and name not in gpu_metrics and name not in noref_metrics)
         if skipped:
-            logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), '
-                           'other pyiqa types are not implemented in this build', skipped)
+            logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), niqe needs '
+                           '`pretrained_model_path` (a local niqe_pris_params.npz), other pyiqa types are not implemented in this build',
+                           skipped)
         n = 0
         for val_data in dataloader:
             img_name = os.path.splitext(os.path.basename(val_data['lq_path'][0]))[0]
@@ -197,6 +398,8 @@ class FeMaSRModel:
                 if save_as_dir:
                     os.makedirs(save_as_dir, exist_ok=True)
                     Image.fromarray(sr_img, 'RGB').save(os.path.join(save_as_dir, f'{img_name}.png'))
+            for name, fn in noref_metrics.items():
+                self.metric_results[name] += fn(sr_u8)
             if metrics and hasattr(self, 'gt'):
                 gt_u8 = imgproc.output_to_u8(self.gt)
                 for name, fn in pixel_metrics.items():

@@ -59,7 +59,7 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -401,6 +401,39 @@ int femasr_psnr_ssim_workspace_bytes(int B, int H, int W, int crop_border, int t
 int femasr_psnr_ssim(void *stream, const uint8_t *a, const uint8_t *b, int B, int H, int W, int crop_border, int test_y, double *psnr_out,
                      double *ssim_out, double *mse_out, void *ws, size_t ws_bytes);
 int femasr_ssim_window(double *win);
+
+/* ---- imresize: MATLAB-style bicubic resize (basicsr/utils/matlab_functions.py:86), two passes over host-built tables ----
+ * in: N planes of (H,W), float32 (is_f64 = 0) or float64 (1), back to back; out: (N,Ho,Wo) of the same type.  The H pass runs first, then the
+ * W pass.  w_h, idx_h: (Ho,taps_h) weights and 0-based source rows of every output row, the symmetric padding already folded into the
+ * indices (femasr_amd.models.femasr_model.imresize_tables builds them in fp64 for any scale and both antialiasing settings, and refuses a
+ * length whose reflected index leaves the image); w_w, idx_w: (Wo,taps_w) likewise.  All four are DEVICE arrays.  Each output is one fp64
+ * accumulator over its taps in ascending order from 0.0, no fma: the float64 output is the definition's (femasr_model.imresize) bit for bit,
+ * the float32 output that value rounded once.  An index outside [0, n) is clamped (memory safety for a bad table; the result is then not
+ * the definition's).  Refused with FEMASR_ERR_INVALID before any launch: an empty shape, N > 65535, a plane or a table of 2^31 elements or
+ * more.  `ws` >= workspace_bytes (the fp64 intermediate, N Ho W), 256-byte aligned.  Two launches on `stream`, nothing allocated. */
+int femasr_imresize_workspace_bytes(int N, int H, int W, int Ho, int Wo, size_t *bytes);
+int femasr_imresize(void *stream, const void *in, int is_f64, int N, int H, int W, int Ho, int Wo, const double *w_h, const int32_t *idx_h,
+                    int taps_h, const double *w_w, const int32_t *idx_w, int taps_w, void *out, void *ws, size_t ws_bytes);
+
+/* ---- NIQE features: validation's no-reference 'niqe' metric (scripts/metrics/calculate_niqe.py) ----
+ * img: B (H,W,3) uint8 RGB HWC images back to back.  crop_border c keeps [c:H-c, c:W-c]; of that the top-left 96 nh x 96 nw pixels
+ * (nh = (H-2c) / 96, nw likewise) are scored.  All fp64 on the device, the definition being femasr_model.niqe_features:
+ *   y = rint(((65.481 R + 128.553 G) + 24.966 B) / 255 + 16); per scale mu, sigma over the 7x7 `window` (49 fp64, row-major, as given:
+ *   scipy.ndimage.convolve(mode='nearest') order) and z = (y - mu) / (sigma + 1); the second scale's plane is imresize(y / 255, 0.5) * 255
+ *   through the tables w_h, idx_h (48 nh, taps_h) and w_w, idx_w (48 nw, taps_w) of femasr_imresize.  y and z of both scales are the
+ *   definition's bits (femasr_niqe_plane_offsets: byte offsets of y, z, y2, z2 in `ws` after a call).
+ *   features[B][nh nw][36]: per block (index iw nh + ih) and scale the 18 AGGD features; positions[B][nh nw][10]: per scale the grid
+ *   position of each of the 5 alphas in arange(0.2, 10.001, 0.001).  `tables`: 5 x 9801 fp64: r_gam, gamma(1/gam), gamma(2/gam),
+ *   gamma(3/gam), gam (femasr_model.aggd_tables).  Moments are summed in a fixed order that depends only on the block's own pixels: the
+ *   features agree with the definition to rounding (1e-10 relative), are run-to-run deterministic and batch-invariant.
+ * window, tables and the resize tables are DEVICE arrays.  Six launches on `stream`, no atomics, no host synchronisation, nothing
+ * allocated.  Refused with FEMASR_ERR_INVALID before any launch: B < 1, B > 65535, crop_border < 0 or leaving nothing, fewer than one
+ * 96x96 block after the crop, B H W 3 >= 2^31.  `ws` >= workspace_bytes (32 bytes per scored pixel), 256-byte aligned. */
+int femasr_niqe_workspace_bytes(int B, int H, int W, int crop_border, size_t *bytes);
+int femasr_niqe_plane_offsets(int B, int H, int W, int crop_border, size_t offsets[4]);
+int femasr_niqe_features(void *stream, const uint8_t *img, int B, int H, int W, int crop_border, const double *window, const double *tables,
+                         const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w, int taps_w,
+                         double *features, int32_t *positions, void *ws, size_t ws_bytes);
 
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
