@@ -19,6 +19,21 @@ int femasr_set_error(int code, const char *fmt, ...);
         if (!(cond)) return femasr_set_error(FEMASR_ERR_INVALID, __VA_ARGS__);            \
     } while (0)
 
+// A launch with more than 64 KiB of dynamic LDS needs the kernel's MaxDynamicSharedMemorySize raised first.  The attribute is per device:
+// *devs holds one bit per device on which `kern` already has it (one mask per kernel, zero-initialised).  Idempotent: a race between
+// threads only repeats the call.
+inline int femasr_allow_dynamic_lds(const void *kern, unsigned long long *devs, size_t bytes)
+{
+    int dev = 0;
+    FEMASR_CHECK_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !((__atomic_load_n(devs, __ATOMIC_ACQUIRE) >> dev) & 1ull)) {
+        FEMASR_CHECK_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        if (dev >= 0 && dev < 64) __atomic_fetch_or(devs, 1ull << dev, __ATOMIC_RELEASE);
+    }
+    return FEMASR_OK;
+}
+#define FEMASR_CHECK(expr) do { const int _rc = (expr); if (_rc != FEMASR_OK) return _rc; } while (0)
+
 // conv launcher with the VQ-argmin epilogue option (kernels_conv.hip)
 //   vq_part != nullptr : instead of storing the tile, each block writes, per row, the
 //   first-min (distance, column) over its BN columns of d = (vq_zz[row] + vq_ee[col]) - 2*acc

@@ -1,6 +1,9 @@
 """Register / scratch metadata of every gfx950 kernel in the built objects (llvm-readelf --notes on the code object inside each .o).
 
     python femasr_amd/csrc/kernel_meta.py [--table out.txt]        # print the table; exit 1 if a kernel outside ALLOW_SCRATCH uses scratch
+    python femasr_amd/csrc/kernel_meta.py --diff OTHER_CSRC_DIR [--rename OLD=NEW ...]
+                                                                   # device code of the objects built here against those of another build
+                                                                   # (a refactor must leave it alone); exit 1 if a kernel differs
 
 `build.py` runs `check()` after compiling: a kernel of the DEFAULT launch schedule must not touch scratch memory (spilled VGPRs turn
 into HBM traffic: VERDICT r4 found 228 B per thread in the codebook lookup and accumulator tiles spilled inside a Winograd main loop).
@@ -48,12 +51,12 @@ def demangle_short(name):
     return name[:80]
 
 
-def kernels():
+def kernels(here=HERE):
     rows = []
-    for f in sorted(os.listdir(HERE)):
+    for f in sorted(os.listdir(here)):
         if not f.endswith('.o'):
             continue
-        elf = device_elf(os.path.join(HERE, f))
+        elf = device_elf(os.path.join(here, f))
         if not elf:
             continue
         with tempfile.NamedTemporaryFile(suffix='.co') as t:
@@ -212,7 +215,37 @@ def check_counted_waits(obj=None):
     return problems
 
 
+META = ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size', 'group_segment_fixed_size')
+
+
+def code_of(csrc, objs=None):
+    """{object file: {kernel symbol: ([(mnemonic, operands)], metadata row)}} of the objects built in csrc (objs: only these files)."""
+    meta = {(r['file'], r['name']): tuple(r.get(k) for k in META) for r in kernels(csrc) if objs is None or r['file'] in objs}
+    return {f: {n: ([i[1:] for i in insts], meta[f, n]) for n, insts in disassemble(os.path.join(csrc, f)).items() if (f, n) in meta}
+            for f in sorted({f for f, _ in meta})}
+
+
+def diff(here, there, rename=()):
+    """One line per kernel of the objects present in both builds: (object, symbol here or there, 'same' | 'differs' | 'only here' |
+    'only there').  rename: (symbol there, symbol here) pairs of kernels whose signature changed."""
+    ren = dict(rename)
+    lines = []
+    for f in sorted(set(here) & set(there)):
+        old = {ren.get(n, n): v for n, v in there[f].items()}
+        for n in sorted(set(here[f]) | set(old)):
+            what = 'only here' if n not in old else 'only there' if n not in here[f] else 'same' if here[f][n] == old[n] else 'differs'
+            lines.append((f, n, what))
+    return lines
+
+
 if __name__ == '__main__':
+    if '--diff' in sys.argv:
+        pairs = [tuple(sys.argv[i + 1].split('=', 1)) for i, a in enumerate(sys.argv) if a == '--rename']
+        lines = diff(code_of(HERE), code_of(sys.argv[sys.argv.index('--diff') + 1]), pairs)
+        for f, n, what in lines:
+            print('%-24s %-10s %s' % (f, what, n))
+        print({w: sum(1 for l in lines if l[2] == w) for w in ('same', 'differs', 'only here', 'only there')})
+        sys.exit(1 if any(l[2] == 'differs' for l in lines) else 0)
     rows, bad = check(verbose='--quiet' not in sys.argv)
     if '--table' in sys.argv:
         open(sys.argv[sys.argv.index('--table') + 1], 'w').write(table(rows))

@@ -791,13 +791,11 @@ Variant g_variants[] = {
 constexpr int kNumVariants = sizeof(g_variants) / sizeof(g_variants[0]);
 constexpr int kFirstHalo = 9;
 
-std::atomic<int> g_small_blocks{-1};         // -1: not set (FEMASR_CONV_SMALL_BLOCKS or the default); test hook, process-global
+std::atomic<int> g_small_blocks{-1};         // -1: not set (the default); femasr_conv_small_launch_blocks, test hook, process-global
 // default threshold: 1.5 x the device's CUs (384 on the 256-CU MI355X in SPX mode; a partition with fewer CUs gets its own value)
 int small_blocks_default()
 {
     static const int v = [] {
-        const char *e = getenv("FEMASR_CONV_SMALL_BLOCKS");
-        if (e && atoi(e) >= 0) return atoi(e);
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             return cus + cus / 2;
@@ -936,12 +934,7 @@ int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq
     p.w_up2 = a->w_up2;
     FEMASR_REQUIRE(!a->gn_part || (vi >= kFirstHalo && femasr_gn_fusable(a->Cout)),
                    "conv2d: gn_part (fused GroupNorm partial moments) needs a 3x3 stride-1 halo conv and 32 | Cout, Cout/32 a power of two <= 32");
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((__atomic_load_n(&v.attr_devs, __ATOMIC_ACQUIRE) >> dev) & 1ull)) {      // (idempotent: a race only repeats the call)
-        FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
-        if (dev >= 0 && dev < 64) __atomic_fetch_or(&v.attr_devs, 1ull << dev, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds));
     hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3((unsigned)v.threads), v.lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     if (variant_out) *variant_out = vi;

@@ -30,29 +30,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef FEMASR_TAPTIME
-// debug build only (tools/build_debug.sh): per-wave cycle sums (tap 0..8, barrier, total, prologue, epilogue).  Level 1
-// stamps only prologue / main loop / epilogue (4 s_memtime per wave: negligible intrusion); FEMASR_TAPTIME=2 also
-// stamps every tap and barrier (each stamp drains lgkmcnt, so that mode slows the kernel and is only for ratios).
-__device__ unsigned long long g_taptime[16 * 65536];     // [wave slot][16], plain stores (same-address atomics serialise)
-#define TT_STAMP_ALWAYS(slot)                                       \
-    {                                                                \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        tt[slot] += now_ - tprev;                                    \
-        tprev = now_;                                                \
-    }
-#if FEMASR_TAPTIME >= 2
-#define TT_STAMP(slot) TT_STAMP_ALWAYS(slot)
-#else
-#define TT_STAMP(slot) {}
-#endif
-__constant__ int g_dbg16_flags;     // debug build only: 1 = skip the prologue's residual loads, 2 = skip its first patch loads
-#define DBG16_ON(bit) (g_dbg16_flags & (bit))
-#else
-#define TT_STAMP(slot) {}
-#define TT_STAMP_ALWAYS(slot) {}
-#define DBG16_ON(bit) false
-#endif
 
 namespace {
 
@@ -101,11 +78,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     unsigned short *Ps = smem_u16;               // [2][2][PP][PPITCH]
 
     const int t = threadIdx.x, lane = t & 63;
-#ifdef FEMASR_TAPTIME
-    unsigned long long tt[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-    const unsigned long long tstart = tprev;
-#endif
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
@@ -191,7 +163,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     };
     f32x16 acc[TM][TN];
     const float *ra = p.res1 ? p.res1 : p.res2, *rb = (p.res1 && p.res2) ? p.res2 : nullptr;
-    if (ra && !DBG16_ON(1)) {
+    if (ra) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -214,7 +186,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     const size_t wstride = (size_t)p.NT32 << 8;     // uint4 per K chunk
 
     const int ncc = p.Cin / BK;
-    if (!DBG16_ON(2)) load_patch(0, 0);
+    load_patch(0, 0);
     uint4 bc[TN][4];
 #pragma unroll
     for (int j = 0; j < TN; ++j)
@@ -223,7 +195,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     if (PRO == FEMASR_PRO_GN_SILU) __syncthreads();     // gco visible
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        if (g > 0 && !DBG16_ON(2)) load_patch(0, g);
+        if (g > 0) load_patch(0, g);
 #pragma unroll
         for (int i = 0; i < GS; ++i)
             if (g * GS + i < PUNITS) store_patch_unit(0, g * GS + i, 0);
@@ -275,7 +247,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] += bv;
         }
-    TT_STAMP_ALWAYS(11)
     for (int cc = 0; cc < ncc; ++cc) {
         const unsigned short *Pb = Ps + (SB ? 0 : ((cc & 1) * 2) * HALF) + koff;
         const int ccn = cc + 1 < ncc ? cc + 1 : cc;
@@ -288,7 +259,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
             for (int i = 0; i < TM; ++i) a_hi[i] = *reinterpret_cast<const uint4 *>(Pb + aidx[i]);
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                if (tap > 0) TT_STAMP(tap - 1)
                 const int q1 = cc * 9 + tap + 1;
                 const size_t qn = (size_t)(q1 < nq ? q1 : nq - 1);
                 if (tap == 0) load_patch(ccn, 0);
@@ -352,7 +322,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
             }
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
-                if (tap > 0) TT_STAMP(tap - 1)
                 const int q1 = cc * 9 + tap + 1;
                 const size_t qn = (size_t)(q1 < nq ? q1 : nq - 1);
                 if (tap == 0) load_patch(ccn, 0);
@@ -409,13 +378,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
                 for (int i = 0; i < PUNITS; ++i) store_patch_unit(0, i, ccn);
             }
         }
-        TT_STAMP(8)
         __syncthreads();
-        TT_STAMP(9)
     }
-#if defined(FEMASR_TAPTIME) && FEMASR_TAPTIME < 2
-    TT_STAMP_ALWAYS(0)
-#endif
 
     // ---- epilogue.  Stores are ISSUE-bound (one dword store per accumulator register = 256 B per wave instruction), so
     // each 32x32 tile is transposed through a per-wave LDS scratch (pitch 36 floats: 16-byte rows, conflict-free both
@@ -481,14 +445,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     // Optional fused GroupNorm moments of the output (consumed by the NEXT conv's GN prologue): per (tile, group)
     // partial sums, reduced lane -> group (xor shuffles over the cg lanes of a group, then the two row halves) -> waves
     // (LDS) and written as doubles to stats_part[((n*tiles + tile)*32 + g)*2]; a fixed order, so runs are reproducible.
-#ifdef FEMASR_TAPTIME
-    TT_STAMP_ALWAYS(12)
-    tt[10] = tprev - tstart;
-    if (lane == 0) {
-        const unsigned slot = (blockIdx.x * (WM * WN) + wave) & 65535u;
-        for (int i = 0; i < 13; ++i) g_taptime[slot * 16 + i] += tt[i];
-    }
-#endif
     if (stats_part) {
         const int cg = p.Cout >> 5;                       // channels per group (32 groups): 8 / 4 / 2
         double *red = reinterpret_cast<double *>(smem_u16);   // [WM][BN][2] (patch buffers are dead after the last barrier)
@@ -614,9 +570,6 @@ bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a)
 int femasr_conv_bf16x3_pick_variant(const femasr_conv_args *a)
 {
     int cls = a->Cout > 128 ? 3 : (a->Cout > 64 ? 0 : (a->Cout > 32 ? 1 : 2));
-#ifdef FEMASR_TAPTIME
-    if (getenv("FEMASR_BF16_CLS")) cls = atoi(getenv("FEMASR_BF16_CLS"));      // debug build only: force a tile class
-#endif
     // Cout 33..64 uses the 4-wave 64 px x 32 ch tiling (rows 15..17: +2.5 % / +9 % fused-x2 over the 8-wave rows 3..5)
     return (cls == 1 ? 15 : cls * 3) + (a->up2 ? 2 : a->prologue);
 }
@@ -637,12 +590,7 @@ int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *var
     p.tilesY = (p.Ho + 7) / 8;
     p.MB = a->B * p.tilesX * p.tilesY;
     p.NB = (a->Cout + v.bn - 1) / v.bn;
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((__atomic_load_n(&v.attr_devs, __ATOMIC_ACQUIRE) >> dev) & 1ull)) {      // (idempotent: a race only repeats the call)
-        FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds + 40 * 1024));
-        if (dev >= 0 && dev < 64) __atomic_fetch_or(&v.attr_devs, 1ull << dev, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds + 40 * 1024));
     size_t lds = v.lds + (a->prologue == FEMASR_PRO_GN_SILU ? (size_t)2 * a->Cin * sizeof(float) : 0);
     const size_t epi = 8192 + (size_t)(v.threads / 64) * 32 * 36 * sizeof(float);       // epilogue transpose scratch
     if (lds < epi) lds = epi;
@@ -656,29 +604,6 @@ int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *var
     return FEMASR_OK;
 }
 
-#ifdef FEMASR_TAPTIME
-extern "C" int femasr_debug_set_flags16(int flags)
-{
-    hipMemcpyToSymbol(HIP_SYMBOL(g_dbg16_flags), &flags, sizeof(int));
-    return 0;
-}
-extern "C" int femasr_debug_taptime(unsigned long long *out16, int reset)
-{
-    static unsigned long long host[16 * 65536];
-    if (out16) {
-        hipMemcpyFromSymbol(host, HIP_SYMBOL(g_taptime), sizeof(host));
-        for (int i = 0; i < 16; ++i) out16[i] = 0;
-        for (int w = 0; w < 65536; ++w)
-            for (int i = 0; i < 16; ++i) out16[i] += host[w * 16 + i];
-    }
-    if (reset) {
-        void *d = nullptr;
-        hipGetSymbolAddress(&d, HIP_SYMBOL(g_taptime));
-        hipMemset(d, 0, sizeof(host));
-    }
-    return 0;
-}
-#endif
 
 extern "C" {
 

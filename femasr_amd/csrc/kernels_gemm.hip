@@ -327,7 +327,7 @@ GVariant g_gv[] = { G_CFG(2, 4, 2, true), G_CFG(2, 2, 3, true), G_CFG(1, 4, 2, f
 constexpr int kPerCfg = 7;
 constexpr int kTileOf[] = { 128, 128, 64 };
 constexpr int kNumG = sizeof(g_gv) / sizeof(g_gv[0]);
-std::atomic<int> g_cfg{-1};          // -1: not read yet, -2: automatic, 0 / 1 / 2: forced (FEMASR_GEMM_CFG, femasr_gemm_force_config; test hooks, process-global)
+std::atomic<int> g_cfg{-1};          // negative: automatic, 0 / 1 / 2: forced (femasr_gemm_force_config; test hook, process-global)
 
 // [chunk][n/32][j][lane][t] <- W[n][k]  (torch (out,in) / OIHW with 1x1 taps), zero padded in n
 __global__ void repack_k1_kernel(const float *__restrict__ in, int O, int I, float *__restrict__ out, size_t total)
@@ -353,13 +353,7 @@ int femasr_gemm_variant_count() { return kNumG; }
 
 extern "C" int femasr_gemm_force_config(int cfg)
 {
-    int prev = g_cfg.load();
-    if (prev == -1) {
-        const char *e = getenv("FEMASR_GEMM_CFG");
-        prev = e ? atoi(e) : -2;
-    }
-    g_cfg.store((cfg >= 0 && cfg < kNumG / kPerCfg) ? cfg : -2);
-    return prev;
+    return g_cfg.exchange((cfg >= 0 && cfg < kNumG / kPerCfg) ? cfg : -1);
 }
 const char *femasr_gemm_variant_name(int v) { return (v >= 0 && v < kNumG) ? g_gv[v].name : "?"; }
 
@@ -386,31 +380,20 @@ int femasr_gemm_pick_variant(const femasr_conv_args *a, bool vq)
         const int nres = (a->res1 ? 1 : 0) + (a->res2 ? 1 : 0);
         vi = (a->act == FEMASR_ACT_GELU ? 3 : 0) + nres;
     }
-    if (g_cfg.load() == -1) {
-        const char *e = getenv("FEMASR_GEMM_CFG");          // A/B runs: force one configuration
-        int c0 = e ? atoi(e) : -2;
-        if (c0 >= kNumG / kPerCfg || c0 < 0) c0 = -2;
-        int expect = -1;
-        g_cfg.compare_exchange_strong(expect, c0);
-    }
     // Configuration by tile count.  All tiles of a launch cost the same, so it takes ceil(tiles / resident slots) rounds:
-    //   * fewer 128 x 128 tiles than FEMASR_GEMM_SMALL_TILES (small batches: B = 1 has 82 of them for proj / fc2 on 256 CUs,
+    //   * fewer than kSmallTiles 128 x 128 tiles (small batches: B = 1 has 82 of them for proj / fc2 on 256 CUs,
     //     each a serial chain of K/2 MFMAs per wave): 64 x 64 tiles - 4x the blocks, a quarter of the chain each;
-    //   * (FEMASR_GEMM_TAIL_PCT=90, off by default: 64 x 64 tiles also where 128 x 128 tiles would leave > 10 % of their last
-    //     round empty - proj / fc2 at B = 16, 2.53 rounds of 512.  Stand-alone that wins, proj 119 -> 103 us, fc2 399 -> 381 us;
-    //     in the network the second sub-batch stream already fills those tails and the step gets 0.4 ms SLOWER: 79.65 vs 79.27.)
+    //   * (measured and dropped: 64 x 64 tiles also where 128 x 128 tiles leave > 10 % of their last round empty - proj / fc2 at B = 16 win
+    //     stand-alone, the step gets 0.4 ms SLOWER, 79.65 vs 79.27: the second sub-batch stream already fills those tails)
     //   * otherwise <4,2> (32-deep chunks, 2 blocks per CU) unless the 3-blocks-per-CU configuration <2,3> wastes less of its
     //     last round.
     int cfg = g_cfg.load();
     if (cfg < 0 || (vq && kTileOf[cfg] != 128)) {
         const double tiles = (double)mb128 * nb128;
         auto eff = [&](double slots) { const double r = tiles / slots; return r / (double)(long long)(r + 0.999999); };
-        static const int small_tiles = [] { const char *e = getenv("FEMASR_GEMM_SMALL_TILES"); return e ? atoi(e) : 700; }();
-        // 128 x 128 tiles whose last round would be emptier than this also go to 64 x 64 tiles
-        static const int tail_pct = [] { const char *e = getenv("FEMASR_GEMM_TAIL_PCT"); return e ? atoi(e) : 0; }();
+        constexpr double kSmallTiles = 700.0;
         const double e2 = eff(512.0), e3 = eff(768.0);
-        const bool small = tiles < (double)small_tiles || (e2 > e3 ? e2 : e3) * 100.0 < (double)tail_pct;
-        cfg = (!vq && small) ? 2 : (e3 > e2 + 0.02 ? 1 : 0);
+        cfg = (!vq && tiles < kSmallTiles) ? 2 : (e3 > e2 + 0.02 ? 1 : 0);
     }
     return vi + cfg * kPerCfg;
 }
@@ -435,12 +418,7 @@ int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_e
     const int bt = kTileOf[vi / kPerCfg];
     p.MB = (p.M + bt - 1) / bt; p.NB = (p.N + bt - 1) / bt;
     GVariant &v = g_gv[vi];
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((__atomic_load_n(&v.attr_devs, __ATOMIC_ACQUIRE) >> dev) & 1ull)) {      // (idempotent: a race only repeats the call)
-        FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds));
-        if (dev >= 0 && dev < 64) __atomic_fetch_or(&v.attr_devs, 1ull << dev, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, (size_t)v.lds));
     hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(256), (size_t)v.lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     if (variant_out) *variant_out = vi;

@@ -499,12 +499,7 @@ int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const voi
     p.MB = (p.M + 127) / 128; p.NB = (p.N + 127) / 128;
     const int vi = femasr_gemm_bf16s_pick_variant(a);
     GSVariant &v = g_gsv[vi];
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((__atomic_load_n(&v.attr_devs, __ATOMIC_ACQUIRE) >> dev) & 1ull)) {      // (idempotent: a race only repeats the call)
-        FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES));
-        if (dev >= 0 && dev < 64) __atomic_fetch_or(&v.attr_devs, 1ull << dev, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, GS_LDS_BYTES));
     hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(256), (size_t)GS_LDS_BYTES, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     if (variant_out) *variant_out = vi;

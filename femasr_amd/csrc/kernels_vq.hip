@@ -10,8 +10,10 @@
 //                                  codes whose lower bound does not exceed the row's smallest upper bound.  The exact
 //                                  first-min is always among them (a code outside the set is strictly farther than
 //                                  some code inside it).
-//   pass 2  vq_exact_kernel        evaluates the specified fp32 chain for the surviving (row, code) pairs on the VALU,
-//                                  takes the first-min with the same tie rule, writes idx and z_q = z + (e - z).
+//   pass 2  its exact phase        the same block evaluates the specified fp32 chain for the surviving (row, code) pairs of its
+//                                  128 rows on the VALU, takes the first-min with the same tie rule, writes idx and
+//                                  z_q = z + (e - z).  The candidate lists never leave LDS: the lookup is ONE launch (round 2 ran
+//                                  pass 2 as a kernel of its own behind lists in global memory; profiles/r04_vq_fused.txt).
 //
 // Error bound used by pass 1 (K = e_dim <= 512 products per dot):
 //   bf16 RNE rounding of both operands       |z~e~ - ze| <= (2^-8 + 2^-18) |z||e|      per product
@@ -23,7 +25,7 @@
 //   roundings of magnitude <= 2^-24 (zz + ee + 2|dot|), covered by the per-row slack gz = 2^-20 (zz + ee_max + 2|z||e|max).
 //   A code survives iff  s_j <= min_j s_j + 2 E_row,  s = ee - 2 dot~,  E_row = 2 VQ_EPS |z| |e|max + gz.
 //
-// Rows whose candidate list overflows (more than VQ_CMAX = 32 entries) are marked VQ_ALL and pass 2 evaluates every code
+// Rows whose candidate list overflows (more than VQ_CMAX = 32 entries) are marked VQ_ALL and the exact phase evaluates every code
 // for them: slow, still exact.
 #include "common.h"
 #include <math.h>
@@ -38,7 +40,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int VQ_R = 128;                  // rows per block of pass 1 (4 MFMA column tiles)
-constexpr int VQ_CMAX = 32;                // candidate slots per row (LDS list of pass 1 = the list handed to pass 2)
+constexpr int VQ_CMAX = 32;                // candidate slots per row (LDS list of pass 1; the list femasr_vq_candidates writes out)
 constexpr int VQ_ALL = 0xFFFF;             // count marker: evaluate every code
 constexpr float VQ_EPS = 0.0042f;
 // one-launch form: line staging of the exact phase - per wave two buffers of (8 candidate slots + the rows of z) x 8 rows x 128 B
@@ -93,7 +95,7 @@ struct VqCandParams {
     int D, n_e;
     const uint4 *cbp;
     const float *ee, *en;           // en[n_e], en[n_e + 1] = max ee, max en
-    unsigned short *cand, *cnt;     // !FUSED: the candidate lists, handed to vq_exact_kernel through global memory
+    unsigned short *cand, *cnt;     // !FUSED: the candidate lists, written out (femasr_vq_candidates)
     const float *cb;                // FUSED: the fp32 codebook and the outputs of the lookup
     long long *idx;
     float *zq;
@@ -101,7 +103,7 @@ struct VqCandParams {
 
 __device__ __forceinline__ uint4 ld_code(const uint4 *cbp, int S, int ct, int s, int lane) { return cbp[((size_t)ct * S + s) * 64 + lane]; }
 
-// pass 2: lane = (row, candidate slot); the specified fp32 chain (ORC_KPERM order inside every 8 channels), first-min
+// exact phase: the specified fp32 chain (ORC_KPERM order inside every 8 channels), first-min
 // over the row's candidates with ties to the smaller code, idx and z_q = z + (e[idx] - z).  |z|^2 (one chain, c ascending,
 // as femasr_row_sqsum) is accumulated alongside the first chain of the row.  The chains are latency-bound (each lane
 // streams its own two 2-KB rows): 32-float bursts = one 128-B line per operand, double-buffered.
@@ -155,7 +157,7 @@ __device__ __forceinline__ void vq_chain(const float *zr, const float *er, int D
 // (L2-resident packed codebook, 4-step register ring), 4 B fragments from LDS, 8 MFMAs.
 // Bound per row (see the header): every code's |d - zz - s| <= Erow, s = ee - 2 dot~, Erow = 2 VQ_EPS |z| |e|max + gz;
 // a code survives iff s <= min_j s_j + 2 Erow.
-// FUSED (round 4, the default): the block also runs the EXACT phase for its 128 rows - the lists never leave LDS, idx and z_q are written
+// FUSED (round 4, the lookup): the block also runs the EXACT phase for its 128 rows - the lists never leave LDS, idx and z_q are written
 // here, ONE launch.  The bf16 image is dead after the search; round 5: its LDS becomes per-wave staging buffers through which the candidates'
 // code rows and the rows of z arrive line-coalesced (see the exact phase below), z_q = z + (e - z) is formed from registers.
 template <int NW, bool FUSED>
@@ -543,109 +545,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void vq_candidates_kernel(const Vq
     }
 }
 
-template <int SLOTS>
-__global__ __launch_bounds__(256, 4) void vq_exact_kernel(const float *__restrict__ z, long long M, int D, const float *__restrict__ cb,
-                                                       const float *__restrict__ ee, int n_e,
-                                                       const unsigned short *__restrict__ cand, const unsigned short *__restrict__ cnt,
-                                                       long long *__restrict__ idx, float *__restrict__ zq)
-{
-    constexpr int RPW = 64 / SLOTS;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int rl = lane / SLOTS, sl = lane % SLOTS;
-    const long long wrow0 = ((long long)blockIdx.x * 4 + w) * RPW;
-    if (wrow0 >= M) return;
-    const long long row = wrow0 + rl;
-    const bool rok = row < M;
-    int n = rok ? (int)cnt[row] : 0;
-    const bool all = n == VQ_ALL;
-    if (all) n = 0;
-    int nmax = n;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) nmax = max(nmax, __shfl_xor(nmax, s, 64));
-    const float *zr = z + (size_t)(rok ? row : wrow0) * D;
-    float zzr = 0.f;
-    float bd = INFINITY;
-    int bi = 0x7fffffff;
-    for (int base = 0; base < nmax; base += SLOTS) {
-        const int k = base + sl;
-        const bool act = k < n;
-        int code = 0;
-        float acc = 0.f, zacc = 0.f;
-        if (act) {
-            code = (int)cand[(size_t)row * VQ_CMAX + k];
-            vq_chain(zr, cb + (size_t)code * D, D, acc, zacc);
-        }
-        if (base == 0) zzr = __shfl(zacc, rl * SLOTS, 64);       // slot 0 is active whenever the row has a candidate
-        const float d = (zzr + ee[code]) - 2.0f * acc;
-        if (act && (d < bd || (d == bd && code < bi))) { bd = d; bi = code; }
-    }
-    // rows marked "every code": the whole wave scans the codebook, 64 codes per step
-    unsigned long long allmask = __ballot(all && sl == 0);
-    while (allmask) {
-        const int l = __builtin_ctzll(allmask);
-        allmask &= allmask - 1;
-        const float *za = z + (size_t)(wrow0 + l / SLOTS) * D;
-        float wd = INFINITY;
-        int wi = 0x7fffffff;
-        for (int j0 = 0; j0 < n_e; j0 += 64) {
-            const int code = j0 + lane;
-            float acc = 0.f, zacc = 0.f;
-            vq_chain(za, cb + (size_t)code * D, D, acc, zacc);
-            const float d = (zacc + ee[code]) - 2.0f * acc;
-            if (d < wd) { wd = d; wi = code; }                   // ascending codes per lane: strict < keeps the first
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-            const float od = __shfl_xor(wd, s, 64);
-            const int oi = __shfl_xor(wi, s, 64);
-            if (od < wd || (od == wd && oi < wi)) { wd = od; wi = oi; }
-        }
-        if (lane == l) { bd = wd; bi = wi; }
-    }
-#pragma unroll
-    for (int s = SLOTS / 2; s >= 1; s >>= 1) {
-        const float od = __shfl_xor(bd, s, 64);
-        const int oi = __shfl_xor(bi, s, 64);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
-    bi = bi < 0 ? 0 : (bi >= n_e ? n_e - 1 : bi);       // rows with no finite distance keep the sentinel, as the single-pass path
-    if (rok && sl == 0) idx[row] = (long long)bi;
-    // z_q rows, 4 at a time (loads of all four in flight before the first store)
-    for (int r0 = 0; r0 < RPW; r0 += 4) {
-        float4 zv[4][2], ev[4][2];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = __shfl(bi, (r0 + r) * SLOTS, 64);
-            const long long rr = wrow0 + r0 + r;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = lane * 4 + 256 * j;
-                if (rr < M && c < D) {
-                    zv[r][j] = ld4(z + (size_t)rr * D + c);
-                    ev[r][j] = ld4(cb + (size_t)b * D + c);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long rr = wrow0 + r0 + r;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = lane * 4 + 256 * j;
-                if (rr < M && c < D) {
-                    const float4 zf = zv[r][j], ef = ev[r][j];
-                    float4 q;
-                    q.x = zf.x + (ef.x - zf.x);
-                    q.y = zf.y + (ef.y - zf.y);
-                    q.z = zf.z + (ef.z - zf.z);
-                    q.w = zf.w + (ef.w - zf.w);
-                    *reinterpret_cast<float4 *>(zq + (size_t)rr * D + c) = q;
-                }
-            }
-        }
-    }
-}
-
 constexpr int VQ_NW = 8;
 
 size_t cand_lds_bytes(int n_e, int D, bool fused)
@@ -655,12 +554,6 @@ size_t cand_lds_bytes(int n_e, int D, bool fused)
 }
 
 unsigned long long g_cand_attr_devs[2] = {0ull, 0ull};      // [list-only | one-launch] instantiation: bit = device
-
-int exact_slots()
-{
-    static const int v = [] { const char *e = getenv("FEMASR_VQ_SLOTS"); return (e && atoi(e) == 4) ? 4 : 8; }();      // (thread-safe one-time init)
-    return v;
-}
 
 }  // namespace
 
@@ -702,15 +595,8 @@ size_t femasr_vq_scratch_bytes(int64_t M, int n_e)
 static int launch_candidates(hipStream_t s, const VqCandParams &p, bool fused)
 {
     const int lds = (int)cand_lds_bytes(p.n_e, p.D, fused);
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    const unsigned long long bit = 1ull << (dev & 63);
-    unsigned long long *mask = &g_cand_attr_devs[fused ? 1 : 0];
-    if (!(__atomic_load_n(mask, __ATOMIC_ACQUIRE) & bit)) {
-        FEMASR_CHECK_HIP(hipFuncSetAttribute(fused ? (const void *)vq_candidates_kernel<VQ_NW, true> : (const void *)vq_candidates_kernel<VQ_NW, false>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
-        __atomic_fetch_or(mask, bit, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds(fused ? (const void *)vq_candidates_kernel<VQ_NW, true> : (const void *)vq_candidates_kernel<VQ_NW, false>,
+                                          &g_cand_attr_devs[fused ? 1 : 0], 163840));
     const dim3 grid((unsigned)((p.M + VQ_R - 1) / VQ_R)), block(VQ_NW * 64);
     if (fused) hipLaunchKernelGGL((vq_candidates_kernel<VQ_NW, true>), grid, block, lds, s, p);
     else hipLaunchKernelGGL((vq_candidates_kernel<VQ_NW, false>), grid, block, lds, s, p);
@@ -730,34 +616,17 @@ int femasr_vq_candidates(void *stream, const float *z, int64_t M, int D, const v
     return launch_candidates((hipStream_t)stream, p, false);
 }
 
-// The lookup.  Default: ONE launch (candidate search + exact phase in the same block, FUSED above); FEMASR_VQ_FUSED=0 keeps the round-2
-// form - the candidate lists through global memory to vq_exact_kernel - for A/B.  Same results bit for bit.
+// The lookup: ONE launch (candidate search + exact phase in the same block, FUSED above).  `scratch` is not touched (it stays in the
+// interface: femasr_vq_scratch_bytes sizes the arena slot the single-pass path uses).
 int femasr_vq_twopass(void *stream, const float *z, int64_t M, int D, const float *cb, const void *aux, const float *ee, int n_e,
                       int64_t *idx, float *zq, void *scratch)
 {
     FEMASR_REQUIRE(z && cb && aux && ee && idx && zq && scratch && M > 0, "vq_twopass: bad args");
     FEMASR_REQUIRE(M < (1ll << 31) - 256, "vq: too many rows");
     FEMASR_REQUIRE(femasr_vq_twopass_ok(n_e, D), "vq_twopass: shape (n_e=%d, e_dim=%d) not supported", n_e, D);
-    hipStream_t s = (hipStream_t)stream;
-    static const bool fused = [] { const char *e = getenv("FEMASR_VQ_FUSED"); return !(e && atoi(e) == 0); }();      // (thread-safe one-time init)
     const float *en = (const float *)((const char *)aux + (size_t)n_e * D * 2);
-    if (fused) {
-        VqCandParams p{z, (long long)M, D, n_e, (const uint4 *)aux, ee, en, nullptr, nullptr, cb, (long long *)idx, zq};
-        return launch_candidates(s, p, true);
-    }
-    const size_t m64 = (size_t)((M + 63) / 64) * 64;
-    uint16_t *cand = (uint16_t *)scratch;
-    uint16_t *cnt = cand + m64 * VQ_CMAX;
-    const int rc = femasr_vq_candidates(stream, z, M, D, aux, ee, n_e, cand, cnt);
-    if (rc) return rc;
-    if (exact_slots() == 8)
-        hipLaunchKernelGGL(vq_exact_kernel<8>, dim3((unsigned)((M + 31) / 32)), dim3(256), 0, s, z, (long long)M, D, cb, ee, n_e, cand, cnt,
-                           (long long *)idx, zq);
-    else
-        hipLaunchKernelGGL(vq_exact_kernel<4>, dim3((unsigned)((M + 63) / 64)), dim3(256), 0, s, z, (long long)M, D, cb, ee, n_e, cand, cnt,
-                           (long long *)idx, zq);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    return FEMASR_OK;
+    VqCandParams p{z, (long long)M, D, n_e, (const uint4 *)aux, ee, en, nullptr, nullptr, cb, (long long *)idx, zq};
+    return launch_candidates((hipStream_t)stream, p, true);
 }
 
 }  // extern "C"

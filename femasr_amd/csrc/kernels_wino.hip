@@ -28,9 +28,6 @@
 // stores, and accumulates the fused GroupNorm partial moments (fp64) per 16x16 sub-block in the order of orc_gn_coeffs mode 2.
 #define FEMASR_WTT_BUF g_wi_ttbuf
 #include "wino_common.h"
-#ifndef FEMASR_WINO_EPI_FENCE
-#define FEMASR_WINO_EPI_FENCE 1
-#endif
 
 namespace {
 
@@ -107,8 +104,7 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         const int sc = s < p.nsteps ? s : p.nsteps - 1;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            if (FEMASR_WINO_ABL & 1) { rr[i] = make_float4(0.1f * sc, 0.2f, 0.3f, 0.4f); continue; }
-            const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, goff[i], sc * 32, W_NT_IN);
+            const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, goff[i], sc * 32, 0);
             rr[i] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
         }
     };
@@ -117,9 +113,8 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         float *Pb = Ps + buf * W4_PSZ;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            if (FEMASR_WINO_ABL & 64) { asm volatile("" :: "v"(rr[i].x), "v"(rr[i].y), "v"(rr[i].z), "v"(rr[i].w)); continue; }
             float4 v = rr[i];
-            if (PRO == FEMASR_PRO_GN_SILU && !(FEMASR_WINO_ABL & 32)) {
+            if (PRO == FEMASR_PRO_GN_SILU) {
                 const float *ab = ABs + (i == 0 ? 0 : (i == 1 ? zo1 : KINDS * p.Cin)) + s * 8 + 4 * quad;
                 const float4 ga = ld4(ab), gb = ld4(ab + p.Cin);
                 if (FAST) {      // x * rcp(1 + exp2(-x log2 e)), two-wide wherever the instruction set is (v_pk_fma / v_pk_mul / v_pk_add)
@@ -146,11 +141,10 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
             }
         }
     };
-    // Two register sets (FEMASR_WINO_DEEP): the patch requested in step s - at pair 5, behind the step's U requests, because loads return
+    // Two register sets: the patch requested in step s - at pair 5, behind the step's U requests, because loads return
     // in order - is the one staged in step s+1, a whole step later: its HBM latency is never waited for.  (With one set the request of
-    // pair 5 was waited for in the same step's T phase; removing the patch loads altogether was worth 10 %, tools/build_debug.sh abl1.)
+    // pair 5 was waited for in the same step's T phase; a timing-only build without the patch loads was 10 % faster.)
     // The set a step stages is a COMPILE-TIME choice (the main loop is unrolled by two): the wait-count bookkeeping is per register.
-    constexpr bool DEEP = FEMASR_WINO_DEEP != 0;
     float4 rq[3];
 
     // ---- input transform item: tile tm, channel lane&7, rows 3*thalf .. 3*thalf+2 of B^T d (uniform per wave)
@@ -162,7 +156,6 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     // (ds_read2_b32) and v_pk_fma / v_pk_add take them as they are; left to the vectoriser the same arithmetic cost 44 v_mov per step)
     tf2 td[5][3];                                          // the transform item's 5 x 6 patch values (rows 3*thalf.. of the 6x6 patch)
     auto transform_read = [&](int pbuf) {
-        if (FEMASR_WINO_ABL & 4) return;
         const float *src = Ps + pbuf * W4_PSZ + tsrc;
 #pragma unroll
         for (int a = 0; a < 5; ++a)
@@ -171,7 +164,6 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     };
     auto fma2 = [](float c, tf2 x, tf2 y) -> tf2 { return __builtin_elementwise_fma(tf2{c, c}, x, y); };
     auto transform_write = [&](int vbuf) {
-        if (FEMASR_WINO_ABL & 4) return;
         float *dst = Vs + vbuf * W4_VSZ + tdst;
         tf2 r[3][3];
         if (thalf == 0) {        // bt_lo on rows 0..4, two columns at a time (component-wise the same IEEE sequence)
@@ -218,7 +210,6 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     auto pntl = [&](int q) -> int { return q < 8 ? (q & 1) : (wave & 1); };
     auto ldU = [&](int s, int q) -> u32x4_t {       // unconditional, like load_patch
         const int sc = s < p.nsteps ? s : p.nsteps - 1;
-        if (FEMASR_WINO_ABL & 2) return u32x4_t{0x3f003f80u, 0x3e803e00u, 0x3f003f80u, 0x3e803e00u};
         const int pr = (sc * 36 + pcomp(q)) * p.NT32 + 2 * nb + pntl(q);
         return __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, lw, pr << 10, 0);
     };
@@ -244,14 +235,10 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
             if ((q & 1) && q + 1 < 9) an = *reinterpret_cast<const f32x4_t *>(Vb + pcomp(q + 1) * 256);      // one A fragment per component
             const f32x4_t b = __builtin_bit_cast(f32x4_t, q < 3 ? ring[q] : (q < 6 ? early[q - 3] : late[q - 6]));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (FEMASR_WINO_ABL & 8) { asm volatile("" :: "v"(a[e]), "v"(b[e])); continue; }
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc[q], 0, 0, 0);
-            }
+            for (int e = 0; e < 4; ++e) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc[q], 0, 0, 0);
             if (q < 3) ring[q] = ldU(s + 1, q);
             if (q == 5) {      // behind the step's U requests (earlier it delays them: loads return in order)
-                if (!DEEP) load_patch(s + 2);                     // staged in THIS step's T phase: 3 pairs + the transform ahead of its use
-                else if (PAR) load_patch_to(rp, s + 3);           // staged in the NEXT step's T phase, from the other set
+                if (PAR) load_patch_to(rp, s + 3);                // staged in the NEXT step's T phase, from the other set
                 else load_patch_to(rq, s + 3);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -283,7 +270,7 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     }
     __syncthreads();
     store_patch_from(rp, 0, 0);
-    if (DEEP) load_patch_to(rp, 2);              // (set 0 is free again: the patch step 0 stages)
+    load_patch_to(rp, 2);              // (set 0 is free again: the patch step 0 stages)
     if (1 < p.nsteps) store_patch_from(rq, 1, 1);
     __syncthreads();
     transform_read(0);
@@ -304,8 +291,8 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         if (HOIST) transform_read(PAR ^ 1);           // (unconditional: after the last step it transforms a stale patch into a dead buffer)
         __builtin_amdgcn_sched_barrier(0);
         if (s < 24) WTT(64 + 2 * s)
-        auto stage = [&]() {                          // the patch of step s+2 -> buffer PAR (DEEP: from the set of this parity, requested a step ago)
-            if (s + 2 < p.nsteps) { if (DEEP && PAR) store_patch_from(rq, s + 2, PAR); else store_patch_from(rp, s + 2, PAR); }
+        auto stage = [&]() {                          // the patch of step s+2 -> buffer PAR (from the set of this parity, requested a step ago)
+            if (s + 2 < p.nsteps) { if (PAR) store_patch_from(rq, s + 2, PAR); else store_patch_from(rp, s + 2, PAR); }
         };
         if (HOIST) {
             transform_write(PAR ^ 1);
@@ -385,8 +372,8 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             if (k < k0 || k >= k1) continue;
-            dst[k][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 0, k), soff(k, 0, r), W_NT_IO));
-            dst[k][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 1, k), soff(k, 1, r), W_NT_IO));
+            dst[k][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 0, k), soff(k, 0, r), 0));
+            dst[k][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 1, k), soff(k, 1, r), 0));
         }
     };
     auto round = [&](auto fullc, int r) {
@@ -409,62 +396,60 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         const float bv = p.bias[n0 + 32 * r + c31];
         __syncthreads();
         WTT(3 + 4 * r)
-        if (!(FEMASR_WINO_ABL & 16)) {
-            // component stride: 16 tile pairs x 32 channels = 4 KiB; three bases keep every read inside the 64-KiB offset field
-            int so1 = (16 * 512 + pi * 32 + c31) * 8, so2 = (32 * 512 + pi * 32 + c31) * 8;
-            asm volatile("" : "+v"(so1), "+v"(so2));
-            const tf2 *src0 = reinterpret_cast<const tf2 *>(Mx) + pi * 32 + c31;
-            const tf2 *src1 = reinterpret_cast<const tf2 *>(reinterpret_cast<const char *>(Mx) + so1), *src2 = reinterpret_cast<const tf2 *>(reinterpret_cast<const char *>(Mx) + so2);
-            auto mx = [&](int c) -> tf2 { return c < 16 ? src0[c * 512] : (c < 32 ? src1[(c - 16) * 512] : src2[(c - 32) * 512]); };
-            tf2 tt[4][6];
+        // component stride: 16 tile pairs x 32 channels = 4 KiB; three bases keep every read inside the 64-KiB offset field
+        int so1 = (16 * 512 + pi * 32 + c31) * 8, so2 = (32 * 512 + pi * 32 + c31) * 8;
+        asm volatile("" : "+v"(so1), "+v"(so2));
+        const tf2 *src0 = reinterpret_cast<const tf2 *>(Mx) + pi * 32 + c31;
+        const tf2 *src1 = reinterpret_cast<const tf2 *>(reinterpret_cast<const char *>(Mx) + so1), *src2 = reinterpret_cast<const tf2 *>(reinterpret_cast<const char *>(Mx) + so2);
+        auto mx = [&](int c) -> tf2 { return c < 16 ? src0[c * 512] : (c < 32 ? src1[(c - 16) * 512] : src2[(c - 32) * 512]); };
+        tf2 tt[4][6];
 #pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                at6(mx(0 * 6 + j), mx(1 * 6 + j), mx(2 * 6 + j), mx(3 * 6 + j), mx(4 * 6 + j), mx(5 * 6 + j), tt[0][j], tt[1][j], tt[2][j], tt[3][j]);
-                if (FEMASR_WINO_EPI_FENCE && (j & 1)) __builtin_amdgcn_sched_barrier(0);
+        for (int j = 0; j < 6; ++j) {
+            at6(mx(0 * 6 + j), mx(1 * 6 + j), mx(2 * 6 + j), mx(3 * 6 + j), mx(4 * 6 + j), mx(5 * 6 + j), tt[0][j], tt[1][j], tt[2][j], tt[3][j]);
+            if (j & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        if (FULL && HAS2) { fetch(fullc, rs_r1, r, r1, 8, 16); fetch(fullc, rs_r2, r, r2, 8, 16); }
+        const tf2 bv2 = {bv, bv};
+        tf2 s2 = {0.f, 0.f}, ss2 = {0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            tf2 y[4];
+            if (!FULL) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (HAS1) fetch(fullc, rs_r1, r, r1, 4 * a, 4 * a + 4);
+                if (HAS2) fetch(fullc, rs_r2, r, r2, 4 * a, 4 * a + 4);
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if (FULL && HAS2) { fetch(fullc, rs_r1, r, r1, 8, 16); fetch(fullc, rs_r2, r, r2, 8, 16); }
-            const tf2 bv2 = {bv, bv};
-            tf2 s2 = {0.f, 0.f}, ss2 = {0.f, 0.f};
+            at6(tt[a][0], tt[a][1], tt[a][2], tt[a][3], tt[a][4], tt[a][5], y[0], y[1], y[2], y[3]);
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                tf2 y[4];
-                if (!FULL) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (HAS1) fetch(fullc, rs_r1, r, r1, 4 * a, 4 * a + 4);
-                    if (HAS2) fetch(fullc, rs_r2, r, r2, 4 * a, 4 * a + 4);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                at6(tt[a][0], tt[a][1], tt[a][2], tt[a][3], tt[a][4], tt[a][5], y[0], y[1], y[2], y[3]);
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int k = 4 * a + b;
-                    tf2 v = y[b] + bv2;
-                    if (HAS1) v = v + r1[k];
-                    if (HAS2) v = v + r2[k];
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), rs_out, voff(fullc, 0, k), soff(k, 0, r), W_NT_IO);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), rs_out, voff(fullc, 1, k), soff(k, 1, r), W_NT_IO);
-                    if (gnp) {
-                        if (!FULL) {
-                            v[0] = __uint_as_float(__float_as_uint(v[0]) & ~oob(0, k));
-                            v[1] = __uint_as_float(__float_as_uint(v[1]) & ~oob(1, k));
-                        }
-                        s2 = s2 + v;
-                        ss2 = __builtin_elementwise_fma(v, v, ss2);
+            for (int b = 0; b < 4; ++b) {
+                const int k = 4 * a + b;
+                tf2 v = y[b] + bv2;
+                if (HAS1) v = v + r1[k];
+                if (HAS2) v = v + r2[k];
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), rs_out, voff(fullc, 0, k), soff(k, 0, r), 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), rs_out, voff(fullc, 1, k), soff(k, 1, r), 0);
+                if (gnp) {
+                    if (!FULL) {
+                        v[0] = __uint_as_float(__float_as_uint(v[0]) & ~oob(0, k));
+                        v[1] = __uint_as_float(__float_as_uint(v[1]) & ~oob(1, k));
                     }
+                    s2 = s2 + v;
+                    ss2 = __builtin_elementwise_fma(v, v, ss2);
                 }
             }
-            if (gnp) {      // fp64 from here
-                double gs = (double)s2[0] + (double)s2[1], gss = (double)ss2[0] + (double)ss2[1];
-                for (int d = 1; d < cg && d < 32; d <<= 1) {
-                    gs = gs + __shfl_xor(gs, d, 64);
-                    gss = gss + __shfl_xor(gss, d, 64);
-                }
-                const double a2 = gs + __shfl_xor(gs, 32, 64), b2 = gss + __shfl_xor(gss, 32, 64);
-                if (lane < 32 && (c31 & (cg - 1)) == 0) {
-                    double *dst = red + ((size_t)wave * 16 + c31 / cg) * 2;
-                    dst[0] = a2;
-                    dst[1] = b2;
-                }
+        }
+        if (gnp) {      // fp64 from here
+            double gs = (double)s2[0] + (double)s2[1], gss = (double)ss2[0] + (double)ss2[1];
+            for (int d = 1; d < cg && d < 32; d <<= 1) {
+                gs = gs + __shfl_xor(gs, d, 64);
+                gss = gss + __shfl_xor(gss, d, 64);
+            }
+            const double a2 = gs + __shfl_xor(gs, 32, 64), b2 = gss + __shfl_xor(gss, 32, 64);
+            if (lane < 32 && (c31 & (cg - 1)) == 0) {
+                double *dst = red + ((size_t)wave * 16 + c31 / cg) * 2;
+                dst[0] = a2;
+                dst[1] = b2;
             }
         }
         WTT(4 + 4 * r)
@@ -542,10 +527,9 @@ __global__ void repack_wino_kernel(const float *__restrict__ in, int O, int I, f
 struct WVariant {
     const char *name;
     void (*kern)(const WinoParams);
-    unsigned long long attr_devs;
-    size_t attr_lds;
+    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d
 };
-#define FEMASR_WINO(PRO, FAST, NRES) { "conv3x3_wino4<2x16x16px x64," #PRO "," #FAST ",res=" #NRES ",waves=8>", conv3x3_wino4_kernel<PRO, FAST, NRES>, 0ull, 0 }
+#define FEMASR_WINO(PRO, FAST, NRES) { "conv3x3_wino4<2x16x16px x64," #PRO "," #FAST ",res=" #NRES ",waves=8>", conv3x3_wino4_kernel<PRO, FAST, NRES>, 0ull }
 #define FEMASR_WINO3(PRO, FAST) FEMASR_WINO(PRO, FAST, 0), FEMASR_WINO(PRO, FAST, 1), FEMASR_WINO(PRO, FAST, 2)
 WVariant g_wv[] = {                               // index = 3 * (prologue form) + residual operands
     FEMASR_WINO3(FEMASR_PRO_NONE, false),
@@ -561,7 +545,7 @@ constexpr int kNumW = sizeof(g_wv) / sizeof(g_wv[0]);
 bool femasr_conv_wino_shape_ok_lim(const femasr_conv_args *a, int log2_total, int log2_image)
 {
     const size_t tot = (size_t)1 << log2_total, img = (size_t)1 << log2_image;
-    return a->ksz == 3 && a->stride == 1 && a->pad == 1 && !a->up2 && a->act == FEMASR_ACT_NONE && (a->Cin % BK) == 0 && a->Cin <= 1024 &&
+    return a->ksz == 3 && a->stride == 1 && a->pad == 1 && !a->up2 && a->act == FEMASR_ACT_NONE && (a->Cin % BK) == 0 && a->Cin <= W4_MAX_CIN &&
            (a->Cout % 64) == 0 && (a->prologue == FEMASR_PRO_NONE || a->prologue == FEMASR_PRO_GN_SILU) &&
            (size_t)a->B * a->H * a->W * a->Cin < tot && (size_t)a->B * a->H * a->W * a->Cout < tot &&
            (size_t)a->H * a->W * a->Cin < img &&          // two images within the 2 GiB range of the input descriptor
@@ -599,22 +583,11 @@ int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *varia
     p.NT32 = a->Cout / 32;
     FEMASR_REQUIRE(a->res1 || !a->res2, "conv_wino: res2 without res1");
     FEMASR_REQUIRE(!a->in_add, "conv_wino: in_add is only taken by the x2 form");
-    if (flops_out) *flops_out = 2.0 * (double)a->B * a->H * a->W * 9.0 * (double)a->Cin * (double)a->Cout;      // ALGORITHMIC, see below
     const int vi = femasr_conv_wino_pick_variant(a);
     WVariant &v = g_wv[vi];
+    // the attribute is only a cap: set once per device to the kernel's maximum; the launch asks for what this shape uses
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, wino_lds_bytes(W4_MAX_CIN, true)));
     const size_t lds = wino_lds_bytes(a->Cin, gn);
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    {   // the attribute is per device and grows with Cin (GN table): bookkeeping under a lock (several handles / threads share the variants)
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= 64 || !((v.attr_devs >> dev) & 1ull) || v.attr_lds < lds) {
-            const size_t want = v.attr_lds > lds ? v.attr_lds : lds;
-            FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
-            if (v.attr_lds < want) { v.attr_lds = want; v.attr_devs = 0ull; }
-            if (dev >= 0 && dev < 64) v.attr_devs |= 1ull << dev;
-        }
-    }
     hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(W4_NT), lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     if (variant_out) *variant_out = vi;

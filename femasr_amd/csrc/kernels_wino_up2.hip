@@ -45,15 +45,8 @@ __device__ unsigned long long *g_wu_ttbuf;
 #endif
 
 // (Measured in round 4 and removed: the transform's patch reads at the start of the M phase, or the whole transform inside the M phase -
-// +-1 %, profiles/r04_wino_variants.txt.  Kept: FEMASR_WINO_DEEP, the two-set patch prefetch of kernels_wino.hip.)
-#ifndef FEMASR_WINO_DEEP
-#define FEMASR_WINO_DEEP 1
-#endif
-#ifndef FEMASR_WINO_NT       // experiment: cache-policy bits of the streaming accesses (bit 1 = nt): 1 = input patches, 2 = residual loads / output stores
-#define FEMASR_WINO_NT 0
-#endif
-#define W_NT_IN ((FEMASR_WINO_NT & 1) ? 2 : 0)
-#define W_NT_IO ((FEMASR_WINO_NT & 2) ? 2 : 0)
+// +-1 %, profiles/r04_wino_variants.txt; the nt cache-policy bit on the streaming accesses - slower or +-2 %, profiles/r04_i_wino_nt.txt.
+// Kept: the two-set patch prefetch of kernels_wino.hip.)
 
 namespace {
 
@@ -134,16 +127,15 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         if (ok) goff = (unsigned)((((size_t)(z ? sn[1] - sn[0] : 0) * p.H + y) * p.W + x) * p.Cin + 4 * quad) * 4u;
         sdst = (z * WU_PPIX + pix) * WU_PS + 4 * quad;
     }
-    constexpr bool DEEP = FEMASR_WINO_DEEP != 0;      // two register sets: the patch requested in step s is staged in step s+1 (kernels_wino.hip)
     // ADD: the conv reads in + in2 (the decoder's `x + enc_feats[i]`, femasr_arch.py:361-362): a second request with the same offsets, one
     // packed add pair per unit while staging (zero padding stays zero: both requests return 0 there)
     const __amdgpu_buffer_rsrc_t rsrc_in2 = __builtin_amdgcn_make_buffer_rsrc((void *)((ADD ? p.in2 : p.in) + (size_t)sn[0] * p.H * p.W * p.Cin), 0, 0x7fffffff, 0x00020000);
     struct Unit { f32x4_t a, b; };
-    Unit rp, rq;
+    Unit rp, rq;      // two register sets: the patch requested in step s is staged in step s+1 (kernels_wino.hip)
     auto load_patch_to = [&](Unit &rr, int s) {       // unconditional (steps past the end re-read the last one): the wait counters stay static
         const int sc = s < p.nsteps ? s : p.nsteps - 1;
-        rr.a = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, goff, sc * 32, W_NT_IN));
-        if (ADD) rr.b = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in2, goff, sc * 32, W_NT_IN));
+        rr.a = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in, goff, sc * 32, 0));
+        if (ADD) rr.b = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc_in2, goff, sc * 32, 0));
     };
     auto load_patch = [&](int s) { load_patch_to(rp, s); };
     auto store_patch_from = [&](const Unit &rr, int buf) {
@@ -240,21 +232,20 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
             }
             if (q < 3) ring[q] = ldU(s + 1, q);
             if (q == 4) {      // behind the step's U requests (loads return in order)
-                if (!DEEP) load_patch(s + 2);                     // staged in THIS step's T phase
-                else if (PAR) load_patch_to(rp, s + 3);           // staged in the NEXT step's T phase, from the other set
+                if (PAR) load_patch(s + 3);                       // (set rp) staged in the NEXT step's T phase, from the other set
                 else load_patch_to(rq, s + 3);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
 
-    // ---- prologue: the patches of steps 0 and 1 requested together (two register sets), then - DEEP - the one step 0 stages
+    // ---- prologue: the patches of steps 0 and 1 requested together (two register sets), then the one step 0 stages
     load_patch(0);
     load_patch_to(rq, 1);
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring[q] = ldU(0, q);
     store_patch(0);
-    if (DEEP) load_patch(2);
+    load_patch(2);
     store_patch_from(rq, 1);
     __syncthreads();
     transform_read(0);
@@ -277,8 +268,8 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         __builtin_amdgcn_sched_barrier(0);
         transform_write(PAR ^ 1);
         __builtin_amdgcn_sched_barrier(0);
-        // step s+2 -> the buffer the transform of step s read a barrier ago (DEEP: from the set of this parity, requested a step ago)
-        if (DEEP && PAR) store_patch_from(rq, PAR); else store_patch_from(rp, PAR);
+        // step s+2 -> the buffer the transform of step s read a barrier ago (from the set of this parity, requested a step ago)
+        if (PAR) store_patch_from(rq, PAR); else store_patch_from(rp, PAR);
         issue_early(s + 1);
         __syncthreads();
         if (s < 40) WUTT(16 + s)
@@ -335,8 +326,8 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
             if (k < k0 || k >= k1) continue;
-            dst[k][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 0, k), soff(k, 0, r), W_NT_IO));
-            dst[k][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 1, k), soff(k, 1, r), W_NT_IO));
+            dst[k][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 0, k), soff(k, 0, r), 0));
+            dst[k][1] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, voff(fullc, 1, k), soff(k, 1, r), 0));
         }
     };
     auto round = [&](auto fullc, int r) {
@@ -383,13 +374,8 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
                     tf2 v = y[b] + bv2;
                     if (HAS1) v = v + r1[k];
                     if (HAS2) v = v + r2[k];
-#ifdef FEMASR_WUP_NOSTORE          // experiment: everything but the output stores (tools/build_debug.sh)
-                    if (p.nsteps < 0)
-#endif
-                    {
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), rs_out, voff(fullc, 0, k), soff(k, 0, r), W_NT_IO);
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), rs_out, voff(fullc, 1, k), soff(k, 1, r), W_NT_IO);
-                    }
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[0]), rs_out, voff(fullc, 0, k), soff(k, 0, r), 0);
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[1]), rs_out, voff(fullc, 1, k), soff(k, 1, r), 0);
                     if (gnp) {
                         if (!FULL) {
                             v[0] = __uint_as_float(__float_as_uint(v[0]) & ~oob(0, k));
@@ -535,12 +521,7 @@ int femasr_conv_wino_up2_launch(hipStream_t s, const femasr_conv_args *a, double
     FEMASR_REQUIRE(a->res1 || !a->res2, "conv_wino_up2: res2 without res1");
     const int nres = (a->res1 ? (a->res2 ? 2 : 1) : 0) + (a->in_add ? 3 : 0);      // (index into the instantiation table)
     const size_t lds = wino_up_lds_bytes();
-    int dev = 0;
-    FEMASR_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !((__atomic_load_n(&g_attr_devs[nres], __ATOMIC_ACQUIRE) >> dev) & 1ull)) {
-        FEMASR_CHECK_HIP(hipFuncSetAttribute((const void *)g_wu_kern[nres], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) __atomic_fetch_or(&g_attr_devs[nres], 1ull << dev, __ATOMIC_RELEASE);
-    }
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)g_wu_kern[nres], &g_attr_devs[nres], lds));
     hipLaunchKernelGGL(g_wu_kern[nres], dim3((unsigned)(p.MB * p.NB)), dim3(WU_NT), lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     // ALGORITHMIC flops (the definition's 9 taps per output pixel, like every other conv launcher); the kernel issues 25/144 of them

@@ -1,4 +1,4 @@
-// wino_common.h - launch parameters, LDS geometry, the 6-point transforms and the experiment switches of the F(4x4,3x3) kernel
+// wino_common.h - launch parameters, LDS geometry and the 6-point transforms of the F(4x4,3x3) kernel
 // (kernels_wino.hip: 2 x 16x16 pixels x 64 output channels per block).  Round 4's second block shape (16x16 pixels x 128 channels,
 // kernels_wino_c128.hip: 7 % fewer cycles, 3 % more time at the 1400 W package limit) was removed in round 6; git history and profiles/r04_j_* have it.
 // The including file defines FEMASR_WTT_BUF (the name of its cycle-stamp buffer) first.
@@ -7,8 +7,6 @@
 #include "detmath.h"
 #include <stdlib.h>
 #include <type_traits>
-#include <atomic>
-#include <mutex>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
@@ -52,11 +50,14 @@ constexpr int W4_MX = 36 * 32 * 32;               // epilogue: one 32-column til
 constexpr int W4_RED = 8 * 2 * 16 * 2 * 2;        // floats: [8 waves][2 sub-blocks][<= 16 groups][2] doubles
 constexpr int W4_UNITS_SB = W4_PPIX * 2;          // float4 staging units per sub-block and step (648)
 
-inline size_t wino_lds_bytes(int cin, bool gn)
+constexpr int W4_MAX_CIN = 1024;                  // femasr_conv_wino_shape_ok
+
+constexpr size_t wino_lds_bytes(int cin, bool gn)
 {
     const size_t main_f = (size_t)W4_MAIN + (gn ? 4 * (size_t)cin : 0), epi_f = (size_t)W4_MX + W4_RED;
     return (main_f > epi_f ? main_f : epi_f) * sizeof(float);
 }
+static_assert(wino_lds_bytes(W4_MAX_CIN, true) <= 160 * 1024, "the largest request (GN table of W4_MAX_CIN channels) must fit the CU's 160 KiB of LDS");
 
 // 6-point transforms of F(4x4,3x3).  Input rows of B^T (Lavin & Gray), written so that each value is one fixed sequence of
 // IEEE operations (the oracle restates them literally):
@@ -114,15 +115,8 @@ __device__ __forceinline__ float wino_g6(int r, float g0, float g1, float g2)
 //   * the input transform on (tile, channel PAIR) items - both passes packed, 72 instead of 2 x 57 instructions per SIMD and step, but
 //     only on waves 0-3: 2 - 9 % SLOWER: one wave's VALU stream alone does not reach the issue rate two interleaved waves do;
 //   * prologue: every global request first, the patches of steps 0 and 1 requested together (second register set): 1 % faster - kept;
-//   * FEMASR_WINO_DEEP (below): the second register set also used in the main loop - see the main loop.
-#ifndef FEMASR_WINO_DEEP
-#define FEMASR_WINO_DEEP 1
-#endif
-#ifndef FEMASR_WINO_NT       // experiment: cache-policy bits of the streaming accesses (bit 1 = nt): 1 = input patches, 2 = residual loads / output stores
-#define FEMASR_WINO_NT 0
-#endif
-#define W_NT_IN ((FEMASR_WINO_NT & 1) ? 2 : 0)
-#define W_NT_IO ((FEMASR_WINO_NT & 2) ? 2 : 0)
-#ifndef FEMASR_WINO_ABL      // ablation experiments (tools/build_debug.sh): bit 0 no patch loads, 1 no U loads, 2 no transform, 3 no MFMAs,
-#define FEMASR_WINO_ABL 0    // 4 no output items, 5 no activation, 6 no staging stores
-#endif
+//   * the second register set also used in the main loop - kept, see the main loop;
+//   * the nt cache-policy bit on the streaming accesses: 5 - 18 % SLOWER on the input patches, +-2 % on the residual loads / output
+//     stores (profiles/r04_i_wino_nt.txt);
+//   * ablation builds (no patch loads, no U loads, no transform, no MFMAs, no output items, no activation, no staging stores; timings
+//     only, results garbage) gave the per-phase costs quoted in the kernels' comments.

@@ -249,7 +249,8 @@ int femasr_row_sqsum(void *stream, const float *x, int64_t rows, int D, float *o
  * few codes per row that can be the fp32 first-min; the specified fp32 chain is then evaluated for those only.
  * Results are bit-identical to femasr_vq.  Shapes: e_dim a power of two in 64..512, n_e % 64 == 0, n_e <= 1024
  * (femasr_vq_twopass_ok); aux = femasr_vq_prepare(cb, ee) image of femasr_vq_aux_bytes bytes;
- * scratch >= femasr_vq_scratch_bytes(M, n_e) bytes (covers femasr_vq too). */
+ * scratch >= femasr_vq_scratch_bytes(M, n_e) bytes (covers femasr_vq too).  femasr_vq_twopass is ONE launch that keeps its
+ * candidate lists on chip: it requires a non-null `scratch` and never reads or writes it (the argument stays in the ABI). */
 int femasr_vq_twopass_ok(int n_e, int D);
 size_t femasr_vq_aux_bytes(int n_e, int D);
 int femasr_vq_prepare(void *stream, const float *cb, const float *ee, int n_e, int D, void *aux);

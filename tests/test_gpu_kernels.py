@@ -374,6 +374,22 @@ def test_conv_winograd_bit_exact(cuda_device, cin, cout, shape, gn, nres, part):
         _same(bb, b_ref, 'fused gn b (winograd)')
 
 
+def test_conv_winograd_largest_lds_after_small(cuda_device):
+    """The F(4x4) kernel's dynamic-LDS cap is set once per device to the kernel's maximum, not grown per launch: on ONE instantiation
+    (GroupNorm prologue, exact SiLU, no residual) a Cin = 32 launch and then the largest request - Cin = 1024 (the shape rule's cap: 128
+    k-steps, a 141 952-byte main-loop image with its GroupNorm table) on 1 x 8 x 20 (one sub-block pair, a border block) - both match the
+    oracle's restatement bit for bit."""
+    import gpu_utils as G
+    for cin, (b, h, w) in ((32, (1, 16, 16)), (1024, (1, 8, 20))):
+        x = synth.uniform(27, f'wlx{cin}', (b, h, w, cin), -2.0, 2.0)
+        wt = synth.uniform(27, f'wlw{cin}', (3, 3, cin, 64), -0.1, 0.1)
+        bias = synth.uniform(27, f'wlb{cin}', (64,), -0.5, 0.5)
+        ga = synth.uniform(27, f'wlga{cin}', (b, cin), 0.5, 1.5)
+        gb = synth.uniform(27, f'wlgb{cin}', (b, cin), -0.5, 0.5)
+        y = G.conv2d(x, wt, bias, 3, 1, 1, prologue=_lib.PRO_GN_SILU, pro=(ga, gb, None), wino=True)
+        _same(y, orc.conv2d(orc.scale_shift_silu(x, ga, gb), wt, bias, 3, 1, 1, wino=True), f'winograd conv, Cin = {cin}')
+
+
 @pytest.mark.parametrize('cin,cout,shape,nres,part', [(32, 64, (1, 8, 8), 0, False), (64, 128, (2, 9, 13), 1, True), (256, 128, (1, 12, 20), 0, True),
                                                       (128, 64, (3, 5, 7), 2, True), (32, 192, (1, 1, 3), 0, False), (512, 256, (1, 4, 4), 0, True)])
 def test_conv_up2_winograd_bit_exact(cuda_device, cin, cout, shape, nres, part):

@@ -110,3 +110,28 @@ def test_twopass_shape_rule_and_model_default(cuda_device):
     assert lib.femasr_vq_twopass_ok(1024, 512) and lib.femasr_vq_twopass_ok(64, 64)
     assert not lib.femasr_vq_twopass_ok(2048, 512) and not lib.femasr_vq_twopass_ok(1024, 96) and not lib.femasr_vq_twopass_ok(1024, 32)
     assert lib.femasr_vq_aux_bytes(1024, 512) == 1024 * 512 * 2 + 1026 * 4
+
+
+def test_twopass_leaves_scratch_untouched(cuda_device):
+    """femasr_vq_twopass is one launch that keeps its candidate lists in LDS: the `scratch` argument stays in the ABI (include/femasr_hip.h)
+    and is neither read nor written.  M = 130 (one row block and a ragged tail), the smallest e_dim and n_e the search accepts."""
+    import torch
+    from femasr_amd import _lib
+    lib = _lib.load()
+    m, d, n_e = 130, 64, 64
+    cb = synth.uniform(36, 'tp.cb', (n_e, d), -1.0, 1.0)
+    z = synth.uniform(37, 'tp.z', (m, d), -1.0, 1.0)
+    tz, tcb = torch.from_numpy(z).cuda(), torch.from_numpy(cb).cuda()
+    ee = torch.empty((n_e,), dtype=torch.float32, device='cuda')
+    _lib.check(lib.femasr_row_sqsum(None, _lib.ptr(tcb), n_e, d, _lib.ptr(ee)))
+    aux = torch.empty(int(lib.femasr_vq_aux_bytes(n_e, d)), dtype=torch.uint8, device='cuda')
+    _lib.check(lib.femasr_vq_prepare(None, _lib.ptr(tcb), _lib.ptr(ee), n_e, d, _lib.ptr(aux)))
+    idx = torch.full((m,), -1, dtype=torch.int64, device='cuda')
+    zq = torch.full((m, d), float('nan'), dtype=torch.float32, device='cuda')
+    scratch = torch.full((int(lib.femasr_vq_scratch_bytes(m, n_e)),), 0xA5, dtype=torch.uint8, device='cuda')
+    _lib.check(lib.femasr_vq_twopass(None, _lib.ptr(tz), m, d, _lib.ptr(tcb), _lib.ptr(aux), _lib.ptr(ee), n_e,
+                                     _lib.ptr(idx), _lib.ptr(zq), _lib.ptr(scratch)))
+    torch.cuda.synchronize()
+    assert bool((scratch == 0xA5).all()), f'{int((scratch != 0xA5).sum())} of {scratch.numel()} scratch bytes were written'
+    idx_ref, zq_ref = orc.vq(z, cb)
+    assert np.array_equal(idx.cpu().numpy(), idx_ref) and np.array_equal(zq.cpu().numpy().view(np.uint32), zq_ref.view(np.uint32))

@@ -1,7 +1,7 @@
 """Micro-benchmark of ONE conv through the C ABI (femasr_conv2d) with device-resident synthetic tensors.
 Usage: python tools/bench_conv.py B H W Cin Cout [--up2] [--gn] [--res] [--fp32] [--k1] [--gelu] [--iters N] [--gn-part]
 Prints ms per launch and algorithmic TFLOP/s.  With FEMASR_SO=tools/dbg/libfemasr_hip_tt.so (tools/build_debug.sh) it also
-prints the per-wave cycle shares and honours FEMASR_BF16_CLS (tile class), FEMASR_DBG / FEMASR_DBG16 (ablation switches)."""
+prints the per-wave cycle shares."""
 import argparse
 import ctypes
 import os
@@ -156,8 +156,7 @@ def main():
     fl = 2.0 * b * ho * wo * cout * ks * ks * cin
     if tt:
         tt_report(ttbuf.cpu().numpy().reshape(nblk, 2, TTS), cin // 16 if c128 else cin // 8, 9216 if c128 else 4608)
-    print('conv %s dbg=%s cls=%s: %.3f ms  %.1f TFLOP/s (algorithmic)' % (' '.join(sys.argv[1:]), os.environ.get('FEMASR_DBG', '0') + '/' + os.environ.get('FEMASR_DBG16', '0'),
-                                                                    os.environ.get('FEMASR_BF16_CLS', '-'), ms, fl / ms / 1e9))
+    print('conv %s: %.3f ms  %.1f TFLOP/s (algorithmic)' % (' '.join(sys.argv[1:]), ms, fl / ms / 1e9))
 
 
 if __name__ == '__main__':
