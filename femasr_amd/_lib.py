@@ -42,7 +42,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 105      # femasr_version(): femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
+ABI_VERSION = 106      # femasr_version(): femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -94,6 +94,8 @@ SIGNATURES = {
     'femasr_paste_tiles': (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp]),
     'femasr_extract_tiles_u8': (c_int, [vp, vp, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp]),
     'femasr_paste_tiles_u8': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, c_int, c_int, c_int, vp]),
+    'femasr_blend_tiles': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp]),
+    'femasr_blend_tiles_u8': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp]),
     'femasr_concat_resize': (c_int, [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]),
     'femasr_repack_oihw': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
     'femasr_packed_weight_floats': (szt, [c_int, c_int, c_int, c_int]),

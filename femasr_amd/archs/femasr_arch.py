@@ -114,13 +114,14 @@ class _TileFormat(NamedTuple):
     native_bc: Callable     # (batch, channel) -> how the native tile calls take them (the uint8 kernels are RGB only)
     extract: str            # native symbols
     paste: str
+    blend: str              # the opt-in overlap-blend paste (test_tile(..., blend=True))
     forward: str
 
 
 _FP32 = _TileFormat(torch.float32, lambda t: tuple(t.shape), lambda t, y0, y1, x0, x1: t[:, :, y0:y1, x0:x1], lambda b, c: (b, c),
-                    'femasr_extract_tiles', 'femasr_paste_tiles', 'femasr_forward')                 # (B, C, H, W): test / test_tile
+                    'femasr_extract_tiles', 'femasr_paste_tiles', 'femasr_blend_tiles', 'femasr_forward')                 # (B, C, H, W): test / test_tile
 _U8 = _TileFormat(torch.uint8, lambda t: (t.shape[0], t.shape[3], t.shape[1], t.shape[2]), lambda t, y0, y1, x0, x1: t[:, y0:y1, x0:x1, :],
-                  lambda b, c: (b,), 'femasr_extract_tiles_u8', 'femasr_paste_tiles_u8', 'femasr_forward_u8')   # (B, H, W, 3): test_u8 / test_tile_u8
+                  lambda b, c: (b,), 'femasr_extract_tiles_u8', 'femasr_paste_tiles_u8', 'femasr_blend_tiles_u8', 'femasr_forward_u8')   # (B, H, W, 3): test_u8 / test_tile_u8
 
 
 def _takes_out(fn):
@@ -522,30 +523,38 @@ class FeMaSRNet(nn.Module):
 
     # ------------------------------------------------------------------ tiled inference
     @torch.no_grad()
-    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True):
+    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False):
         """Reference semantics of femasr_arch.py:387-447 (overlap-discard paste onto a zero canvas), but
         tiles of one shape class run as batched `test()` calls, and with world_size > 1 each rank
         computes a contiguous share of every class; `gather(results, classes, batch, channel, scale) -> list per rank`
         supplies the collective (femasr_amd.distributed.TileExchange: ONE RCCL all-gather on persistent buffers the tiles were
         written into).  paste=False (ranks other than the one that needs the image): take part in the collective, skip the
-        canvas (returns None)."""
-        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste)
+        canvas (returns None).
+        blend=True (NOT the reference's arithmetic, hence off by default): instead of discarding the halos, every canvas pixel is the
+        weighted mean of the upscaled windows that contain it (linear ramps across the overlaps: tiling.blend_weight_1d)
+        - no seams where neighbouring bodies meet.  The tiles, their batching and the collective are the same; only the last step
+        differs (ONE femasr_blend_tiles launch instead of the per-class pastes).  Needs 2 * tile_pad <= tile_size (ValueError)."""
+        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste, blend)
 
     @torch.no_grad()
-    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False):
+    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False, blend=False):
         """`test_tile` on uint8 images end to end (round 6; the CLI's tiled branch, inference_femasr.py:58-67 with femasr_arch.py:387-447):
         uint8 (H,W,3) / (B,H,W,3) in -> uint8 (sH,sW,3) / (B,sH,sW,3) out.  Tiles are cropped as uint8, every batched call is ONE
         `test_u8` (decode fused into the mirror-pad kernel, tensor2img into the crop kernel, which stores straight into the result /
         all-gather send buffer), the all-gather and the paste move one byte per value (a quarter of the fp32 path's xGMI and canvas
         traffic; no 805-MB fp32 canvas at 8192^2).  Bit-identical to output_to_u8(test_tile(u8_to_input(img))): tensor2img is
-        element-wise and every output pixel comes from exactly one tile."""
+        element-wise and every output pixel comes from exactly one tile.
+        blend=True: as in `test_tile`, on the BYTES the tiles hold after tensor2img (the all-gather payload stays one byte per value):
+        the weighted mean of the covering windows' bytes, rounded half to even - not tensor2img of the fp32 blend."""
         x, single = self._u8_batch(img_u8)
-        output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste)
+        output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste, blend)
         return output[0] if single and output is not None else output
 
-    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste):
+    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste, blend=False):
         """The tile schedule of `test_tile` and `test_tile_u8`: `x` is the contiguous image batch in tile format `fmt`,
         `run(crops[, out=])` the batched call on the crops of one shape class.  Returns the canvas (None with paste=False)."""
+        if blend:
+            tiling.check_blend(tile_size, tile_pad)             # before any work
         batch, channel, height, width = fmt.bchw(x)
         s = self.scale_factor
         classes = tiling.shape_classes(tiling.enumerate_tiles(height, width, tile_size, tile_pad))
@@ -585,7 +594,9 @@ class FeMaSRNet(nn.Module):
         if ev:
             ev[2].record()
         output = None
-        if paste:
+        if paste and blend:
+            output = self._blend_tiles(fmt, x, per_rank, owned_all, batch, channel, height, width, tile_size, s)
+        elif paste:
             output = x.new_zeros(tiling.tile_shape(fmt.dtype, batch, channel, height * s, width * s))
             for r, res in enumerate(per_rank):
                 for hw, tl in owned_all[r].items():
@@ -643,3 +654,47 @@ class FeMaSRNet(nn.Module):
         with torch.cuda.device(output.device):
             _lib.check(getattr(_lib.load(), fmt.paste)(torch.cuda.current_stream().cuda_stream, block.data_ptr(), *fmt.native_bc(batch, c),
                                                        len(tl), th, tw, rd.data_ptr(), hmax, oh, ow, output.data_ptr()))
+
+    @staticmethod
+    def _blend_tiles(fmt, x, per_rank, owned_all, batch, channel, height, width, tile_size, s):
+        """The overlap-blend canvas of `test_tile(..., blend=True)` from every rank's tiles: out = sum_k w_k v_k / sum_k w_k over the
+        windows k that contain the pixel, in row-major tile order (tiling.blend_weight_1d).  GPU: ONE gather-form launch
+        over the whole canvas, fed by a table of tile addresses (the tiles stay where the batched calls / the all-gather left them) and
+        the geometry table.  Host tensors (the CPU-side tests of the partition / gather logic): the same definition as a torch loop,
+        fp32 in the kernel's operation order."""
+        where = {}                                  # tile number -> (the block of its rank and class, its place in that block)
+        for r, res in enumerate(per_rank):
+            for hw, tl in owned_all[r].items():
+                for k, t in enumerate(tl):
+                    where[t.index] = (t, res[hw], k)
+        tiles = [where[i][0] for i in range(len(where))]
+        shape = tiling.tile_shape(fmt.dtype, batch, channel, height * s, width * s)
+        if not x.is_cuda:
+            def w32(length, lead, trail):
+                i = torch.arange(length, dtype=torch.int32)
+                one = torch.ones(length)
+                wl = one if lead == 0 else torch.minimum(one, (2 * i + 1).float() / float(4 * lead))
+                wr = one if trail == 0 else torch.minimum(one, (2 * (length - 1 - i) + 1).float() / float(4 * trail))
+                return torch.minimum(wl, wr)
+            acc = torch.zeros(shape)
+            den = torch.zeros(tiling.tile_shape(fmt.dtype, 1, 1, height * s, width * s))
+            for t, block, k in (where[i] for i in range(len(where))):
+                ay, ax, th, tw, ly, ry, lx, rx = tiling.blend_geom(t, s)
+                w = (w32(th, ly, ry)[:, None] * w32(tw, lx, rx)[None, :]).reshape(tiling.tile_shape(fmt.dtype, 1, 1, th, tw))
+                fmt.window(acc, ay, ay + th, ax, ax + tw).add_(w * block[k * batch:(k + 1) * batch].float())
+                fmt.window(den, ay, ay + th, ax, ax + tw).add_(w)
+            out = acc / den
+            return out if fmt.dtype.is_floating_point else out.clamp_(0, 255).round_().to(fmt.dtype)
+        output = torch.empty(shape, dtype=fmt.dtype, device=x.device)          # every element is written once: nothing to zero
+        blocks, ptrs = {}, []
+        for t, block, k in (where[i] for i in range(len(where))):
+            blk = blocks.setdefault(id(block), block.contiguous().to(fmt.dtype))        # (kept alive until the launch is enqueued)
+            th, tw = t.in_hw[0] * s, t.in_hw[1] * s
+            ptrs.append(blk.data_ptr() + k * batch * channel * th * tw * blk.element_size())
+        tab = torch.tensor(ptrs, dtype=torch.int64).to(x.device, non_blocking=True)
+        geo = torch.tensor(tiling.blend_table(tiles, s), dtype=torch.int32).to(x.device, non_blocking=True)
+        ny, nx = math.ceil(height / tile_size), math.ceil(width / tile_size)
+        with torch.cuda.device(x.device):
+            _lib.check(getattr(_lib.load(), fmt.blend)(torch.cuda.current_stream().cuda_stream, tab.data_ptr(), geo.data_ptr(), len(tiles), ny, nx,
+                                                       tile_size * s, *fmt.native_bc(batch, channel), height * s, width * s, output.data_ptr()))
+        return output

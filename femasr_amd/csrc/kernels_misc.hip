@@ -7,6 +7,7 @@
 #include "detmath.h"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 namespace {
 
@@ -808,6 +809,74 @@ __global__ void paste_tiles_u8_kernel(const unsigned char *__restrict__ tiles, i
     for (int x = threadIdx.x; x < 3 * rc[5]; x += blockDim.x) dst[x] = src[x];
 }
 
+// ------------------------------------------------------------------------------------------
+// Overlap-blend paste (NOT the reference's arithmetic; opt-in): every canvas pixel is the weighted mean of the
+// upscaled WINDOWS (halo included) that contain it, tiles visited in row-major order.  Gather form: one thread per canvas element,
+// no atomics, no weight canvas, the canvas is written once and never read.
+// geom[8k..] = (window origin y, x on the canvas, th, tw, leading / trailing margin in y, leading / trailing margin in x) in upscaled
+// pixels (tiling.blend_table); a margin of 0 is an image border.  ptrs[k] = tile k, image 0; image b follows th*tw*channels later.
+// ------------------------------------------------------------------------------------------
+// 1-D weight of window coordinate i in [0, len): a linear ramp over the 2*margin wide overlap, centred on the body edge, sampled at
+// pixel centres; > 0 everywhere, 1 outside the ramps.  One IEEE divide per side (the integers are exact in fp32: below 2^24).
+__device__ __forceinline__ float blend_weight(int i, int len, int lead, int trail)
+{
+    const float wl = lead == 0 ? 1.0f : fminf(1.0f, (float)(2 * i + 1) / (float)(4 * lead));
+    const float wr = trail == 0 ? 1.0f : fminf(1.0f, (float)(2 * (len - 1 - i) + 1) / (float)(4 * trail));
+    return fminf(wl, wr);
+}
+
+// One block = one canvas row (b, c, Y) inside one body-cell column cx: the candidate tiles - the pixel's own cell and its +-1
+// neighbours (2 tile_pad <= tile_size) - depend on the block alone, so the table reads are scalar loads and every tile row is
+// read as one contiguous run along x.  The last cell row / column takes what the canvas has beyond it (hand-made tables only).
+template <bool U8>
+__global__ __launch_bounds__(256) void blend_tiles_kernel(const unsigned long long *__restrict__ ptrs, const int *__restrict__ geom,
+                                                         int tiles_y, int tiles_x, int pitch, int C, int Ho, int Wo, void *__restrict__ out_)
+{
+    using T = typename std::conditional<U8, unsigned char, float>::type;
+    // fp32: rows are (b, c, Y), E = 1 element per pixel; uint8 HWC: rows are (b, Y), E = 3 interleaved elements per pixel
+    const int E = U8 ? 3 : 1;
+    size_t r = blockIdx.x;
+    const int Y = (int)(r % Ho);
+    r /= Ho;
+    const int c = U8 ? 0 : (int)(r % C);
+    const size_t b = U8 ? r : r / C;
+    const int cx = blockIdx.y, cy = min(Y / pitch, tiles_y - 1);
+    const int x0 = cx * pitch, x1 = cx == tiles_x - 1 ? Wo : min(x0 + pitch, Wo);
+    T *dst = (T *)out_ + (size_t)blockIdx.x * Wo * E;
+    for (int j = x0 * E + threadIdx.x; j < x1 * E; j += blockDim.x) {
+        const int X = U8 ? j / 3 : j, ch = U8 ? j - 3 * X : 0;
+        float acc = 0.0f, den = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int ty = cy + dy;
+            if (ty < 0 || ty >= tiles_y) continue;
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int tx = cx + dx;
+                if (tx < 0 || tx >= tiles_x) continue;
+                const int k = ty * tiles_x + tx;
+                const int *g = geom + 8 * k;
+                const int ly = Y - g[0], th = g[2], tw = g[3];
+                if (ly < 0 || ly >= th) continue;                          // (block-uniform)
+                const int lx = X - g[1];
+                if (lx < 0 || lx >= tw) continue;                          // every read stays inside the th x tw tile the table names
+                const float w = blend_weight(ly, th, g[4], g[5]) * blend_weight(lx, tw, g[6], g[7]);
+                const T *t = (const T *)ptrs[k] + b * ((size_t)th * tw * (U8 ? 3 : C));
+                const float v = (float)(U8 ? t[((size_t)ly * tw + lx) * 3 + ch] : t[((size_t)c * th + ly) * tw + lx]);
+                acc = acc + w * v;
+                den = den + w;
+            }
+        }
+        float q = den > 0.0f ? acc / den : 0.0f;                            // (no tile: a hand-made table; 0 like the paste's zero canvas)
+        if (U8) {
+            q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);                   // tensor2img's rounding: half to even
+            dst[j] = (T)rintf(q);
+        } else {
+            dst[j] = (T)q;
+        }
+    }
+}
+
 // out[n,y,x,:] = cat(a[n,y,x,:Ca], b[n, y*Hb/H, x*Wb/W, :Cb]); one thread per float4 of the output (Ca, Cb % 4 == 0)
 __global__ void concat_resize_kernel(const float *__restrict__ a, int Ca, const float *__restrict__ b, int Hb, int Wb, int Cb,
                                      int H, int W, float *__restrict__ out, size_t total4)
@@ -1083,6 +1152,39 @@ int femasr_paste_tiles_u8(void *stream, const uint8_t *tiles, int B, int n, int 
     hipLaunchKernelGGL(paste_tiles_u8_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, tiles, B, th, tw, rects_dev, n, Ho, Wo, out, hmax);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
+}
+
+static int blend_launch(bool u8, void *stream, const uint64_t *tile_ptrs_dev, const int32_t *geom_dev, int n, int tiles_y, int tiles_x,
+                        int pitch, int B, int C, int Ho, int Wo, void *out)
+{
+    const char *who = u8 ? "blend_tiles_u8" : "blend_tiles";
+    FEMASR_REQUIRE(tile_ptrs_dev && geom_dev && out, "%s: null pointer", who);
+    FEMASR_REQUIRE(n > 0 && B > 0 && C > 0 && tiles_y > 0 && tiles_x > 0 && pitch > 0 && Ho > 0 && Wo > 0, "%s: bad sizes", who);
+    FEMASR_REQUIRE((long long)tiles_y * tiles_x == n, "%s: %d tiles given for a %d x %d grid", who, n, tiles_y, tiles_x);
+    FEMASR_REQUIRE(tiles_x <= 65535, "%s: more than 65535 tile columns", who);
+    const size_t rows = (size_t)B * C * Ho;
+    FEMASR_REQUIRE(rows < ((size_t)1 << 31), "%s: too many rows", who);
+    const dim3 grid((unsigned)rows, (unsigned)tiles_x);
+    if (u8)
+        hipLaunchKernelGGL(blend_tiles_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)tile_ptrs_dev,
+                           geom_dev, tiles_y, tiles_x, pitch, 1, Ho, Wo, out);
+    else
+        hipLaunchKernelGGL(blend_tiles_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)tile_ptrs_dev,
+                           geom_dev, tiles_y, tiles_x, pitch, C, Ho, Wo, out);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
+}
+
+int femasr_blend_tiles(void *stream, const uint64_t *tile_ptrs_dev, const int32_t *geom_dev, int n, int tiles_y, int tiles_x, int pitch,
+                       int B, int C, int Ho, int Wo, float *out)
+{
+    return blend_launch(false, stream, tile_ptrs_dev, geom_dev, n, tiles_y, tiles_x, pitch, B, C, Ho, Wo, out);
+}
+
+int femasr_blend_tiles_u8(void *stream, const uint64_t *tile_ptrs_dev, const int32_t *geom_dev, int n, int tiles_y, int tiles_x, int pitch,
+                          int B, int Ho, int Wo, uint8_t *out)
+{
+    return blend_launch(true, stream, tile_ptrs_dev, geom_dev, n, tiles_y, tiles_x, pitch, B, 1, Ho, Wo, out);
 }
 
 int femasr_concat_resize(void *stream, const float *a, int Ca, const float *b, int Hb, int Wb, int Cb, int B, int H, int W, float *out)

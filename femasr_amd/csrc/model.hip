@@ -869,7 +869,7 @@ int check_ready(const femasr_handle *h)
 extern "C" {
 
 const char *femasr_last_error(void) { return g_err; }
-int femasr_version(void) { return 105; }
+int femasr_version(void) { return 106; }
 
 int femasr_create(const femasr_config *cfg, femasr_handle **out)
 {

@@ -28,12 +28,7 @@ def load_weights(model, path):
     return model.load_state_dict(sd, strict=False)
 
 
-def main(argv=None):
-    from PIL import Image
-    from femasr_amd import distributed as fd
-    from femasr_amd import imgproc, synth
-    from femasr_amd.archs.femasr_arch import FeMaSRNet
-
+def build_parser():
     ap = argparse.ArgumentParser(description='FeMaSR inference on MI355X')
     ap.add_argument('-i', '--input', type=str, default='inputs', help='Input image or folder')
     ap.add_argument('-w', '--weight', type=str, default=None, help='path for model weights')
@@ -47,7 +42,19 @@ def main(argv=None):
     ap.add_argument('--streams', type=int, default=3, help='sub-batch streams inside one batched forward of the tiled branch (3 measured fastest on MI355X)')
     ap.add_argument('--decoder-math', choices=['fp32', 'fp32_strict', 'fp32_direct', 'bf16x3'], default='fp32',
                     help="arithmetic of the convs behind the codebook lookup (FeMaSRNet.decoder_math); 'fp32_strict' is bit-identical to the CPU oracle")
-    args = ap.parse_args(argv)
+    ap.add_argument('--blend', action='store_true',
+                    help='tiled branch: blend the overlapping tile halos instead of discarding them (no seams between tiles; NOT the '
+                         "reference's arithmetic, off by default; needs 2 * tile_pad <= tile_size)")
+    return ap
+
+
+def main(argv=None):
+    from PIL import Image
+    from femasr_amd import distributed as fd
+    from femasr_amd import imgproc, synth
+    from femasr_amd.archs.femasr_arch import FeMaSRNet
+
+    args = build_parser().parse_args(argv)
 
     if not torch.cuda.is_available():
         raise SystemExit('femasr_amd.inference needs a GPU (there is no CPU fallback)')
@@ -82,9 +89,9 @@ def main(argv=None):
             # tiled: uint8 tiles in, uint8 tiles out - crops, the all-gather over xGMI and the paste move one byte per value, no fp32 image
             # or canvas is ever held (FeMaSRNet.test_tile_u8); with several ranks only rank 0 pastes
             if world > 1:
-                u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True)
+                u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend)
             else:
-                u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad)
+                u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend)
         if rank == 0:
             Image.fromarray(u8.cpu().numpy(), 'RGB').save(os.path.join(args.output, img_name))
     if world > 1:

@@ -349,7 +349,12 @@ class FeMaSRModel:
     def test(self):
         min_size = 8000 * 8000
         _, _, h, w = self.lq.shape
-        self.output = self.net_g.test(self.lq) if h * w < min_size else self.net_g.test_tile(self.lq)
+        # `val: tile_blend: true` (an extension key, absent = false): the tiled branch blends the tile overlaps (FeMaSRNet.test_tile)
+        blend = bool((self.opt.get('val') or {}).get('tile_blend', False))
+        if h * w < min_size:
+            self.output = self.net_g.test(self.lq)
+        else:
+            self.output = self.net_g.test_tile(self.lq, blend=True) if blend else self.net_g.test_tile(self.lq)
 
     @torch.no_grad()
     def extract_gt_indices(self, gt=None):

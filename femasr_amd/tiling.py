@@ -1,6 +1,6 @@
 """Tile geometry of the reference's tiled inference and its rank partition.
 
-Pure integer host logic (no torch, no GPU) so it is unit-testable on CPU.
+Pure integer host logic (no torch, no GPU; float64 numpy for the blend weights) so it is unit-testable on CPU.
 
 Reference behaviour restated (basicsr/archs/femasr_arch.py:387-447
 `FeMaSRNet.test_tile`): tiles are enumerated row-major over
@@ -19,6 +19,8 @@ import math
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, List, Tuple
+
+import numpy as np
 
 
 @dataclass(frozen=True)
@@ -61,6 +63,42 @@ def enumerate_tiles(height: int, width: int, tile_size: int, tile_pad: int) -> L
                               max(x0 - tile_pad, 0), min(x1 + tile_pad, width),
                               y0, y1, x0, x1))
     return tiles
+
+
+# --------------------------------------------------------------------------- overlap-blend paste (opt-in; NOT the reference's arithmetic)
+# `test_tile(..., blend=True)` keeps the halos the reference discards: every canvas pixel is the weighted mean of the upscaled windows
+# that contain it.  The definition lives here, in integers and float64; femasr_blend_tiles and the host loop of
+# FeMaSRNet._blend_tiles evaluate it in fp32.
+BLEND_FIELDS = 8        # int32 values per tile in `blend_table`
+
+
+def check_blend(tile_size: int, tile_pad: int) -> None:
+    """Blend mode needs 2 * tile_pad <= tile_size: then at most two windows cover a pixel per axis (four in all) and they belong to the
+    pixel's own body cell or its +-1 neighbours."""
+    if tile_size <= 0 or tile_pad < 0 or 2 * tile_pad > tile_size:
+        raise ValueError(f'blend=True needs 0 <= 2 * tile_pad <= tile_size, got tile_size {tile_size}, tile_pad {tile_pad}')
+
+
+def blend_geom(t: Tile, s: int) -> Tuple[int, int, int, int, int, int, int, int]:
+    """(window origin y, x on the upscaled canvas, window height, width, leading / trailing margin in y, leading / trailing margin in x)
+    of one tile at scale `s`; a margin of 0 means that side of the body is the image border."""
+    return (t.y0p * s, t.x0p * s, (t.y1p - t.y0p) * s, (t.x1p - t.x0p) * s,
+            (t.y0 - t.y0p) * s, (t.y1p - t.y1) * s, (t.x0 - t.x0p) * s, (t.x1p - t.x1) * s)
+
+
+def blend_table(tiles: List[Tile], s: int) -> List[int]:
+    """The flat int32 table femasr_blend_tiles takes: `blend_geom` of every tile, in row-major tile order."""
+    assert [t.index for t in tiles] == list(range(len(tiles)))
+    return [v for t in tiles for v in blend_geom(t, s)]
+
+
+def blend_weight_1d(length: int, lead: int, trail: int):
+    """float64 weights of the `length` window coordinates of one axis: a linear ramp across the whole 2 * margin wide overlap, centred on
+    the body edge and sampled at pixel centres; positive everywhere, exactly 1 outside the ramps.  Two regular neighbours' ramps sum to 1."""
+    i = np.arange(length, dtype=np.int64)
+    wl = np.ones(length) if lead == 0 else np.minimum(1.0, (2 * i + 1) / np.float64(4 * lead))
+    wr = np.ones(length) if trail == 0 else np.minimum(1.0, (2 * (length - 1 - i) + 1) / np.float64(4 * trail))
+    return np.minimum(wl, wr)
 
 
 def shape_classes(tiles: List[Tile]) -> "OrderedDict[Tuple[int, int], List[Tile]]":

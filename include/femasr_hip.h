@@ -59,7 +59,7 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  106: femasr_blend_tiles / femasr_blend_tiles_u8 (the opt-in overlap-blend paste).  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -281,6 +281,28 @@ int femasr_paste_tiles(void *stream, const float *tiles, int B, int C, int n, in
 int femasr_extract_tiles_u8(void *stream, const uint8_t *in, int B, int H, int W, const int32_t *yx_dev, int n, int th, int tw, uint8_t *out);
 int femasr_paste_tiles_u8(void *stream, const uint8_t *tiles, int B, int n, int th, int tw, const int32_t *rects_dev, int hmax,
                           int Ho, int Wo, uint8_t *out);
+/* Overlap-blend paste (opt-in, FeMaSRNet.test_tile(..., blend=True); NOT the reference's arithmetic, which discards the halos): every
+ * canvas pixel becomes the weighted mean of the upscaled WINDOWS that contain it,
+ *   out[b,c,Y,X] = sum_k w_k(Y,X) v_k[b,c,Y-Ay_k,X-Ax_k] / sum_k w_k(Y,X),   w_k = wy_k(Y) wx_k(X),
+ * over the covering tiles k in row-major order, with the 1-D weight of window coordinate i in [0, len) and margins lead / trail
+ *   min(lead ? min(1, (2i+1) / (4 lead)) : 1,  trail ? min(1, (2(len-1-i)+1) / (4 trail)) : 1)
+ * (a linear ramp across the overlap, centred on the body edge).  fp32, no contraction: w = (float)num / (float)(4 margin),
+ * acc and den summed from 0 in tile order, out = acc / den; the uint8 form accumulates (float)byte and stores rintf of the quotient
+ * clamped to [0, 255] (half to even, as tensor2img).  One launch per canvas, gather form: no atomics, every canvas element is written
+ * exactly once and never read, so the canvas need not be initialised.
+ *   tile_ptrs_dev[k]  device address of tile k (row-major tile number), image 0: fp32 (C, th, tw) / uint8 (th, tw, 3); image b of the
+ *                     batch follows b * C*th*tw (3*th*tw) elements later - the tile-major layout of femasr_extract_tiles' batches
+ *   geom_dev[8k..]    (window origin y, x on the canvas, th, tw, lead_y, trail_y, lead_x, trail_x) in upscaled pixels; margin 0 = image border
+ *   tiles_y, tiles_x  the tile grid, n == tiles_y * tiles_x;  pitch = tile_size * scale, the body pitch; needs 2 tile_pad <= tile_size, so
+ *                     that only a pixel's own cell and its +-1 neighbours can cover it
+ * Refused with FEMASR_ERR_INVALID before any launch: a null pointer; n, B, C or a size <= 0; n != tiles_y * tiles_x; tiles_x > 65535;
+ * B*C*Ho (uint8: B*Ho) >= 2^31 canvas rows.  The tables are the caller's (tiling.blend_table): the kernel only guarantees that a read
+ * driven by them stays inside the th x tw tile they name (memory safety for a hand-made table, not validation; a pixel that no listed
+ * window contains is written as 0). */
+int femasr_blend_tiles(void *stream, const uint64_t *tile_ptrs_dev, const int32_t *geom_dev, int n, int tiles_y, int tiles_x, int pitch,
+                       int B, int C, int Ho, int Wo, float *out);
+int femasr_blend_tiles_u8(void *stream, const uint64_t *tile_ptrs_dev, const int32_t *geom_dev, int n, int tiles_y, int tiles_x, int pitch,
+                          int B, int Ho, int Wo, uint8_t *out);
 
 /* OIHW -> the packed FRAGMENT-MAJOR weight layout of femasr_conv_args.w (also nn.Linear (out,in) with kh=kw=1
  * and the codebook for femasr_vq):  out[q][ntile][lane][kk], zero padded, with
