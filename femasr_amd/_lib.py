@@ -39,10 +39,11 @@ class ConvArgs(ctypes.Structure):
         ('res1', vp), ('res2', vp), ('out', vp),
         ('Ho', ctypes.c_int32), ('Wo', ctypes.c_int32),
         ('w_bf16x3', vp), ('gn_part', vp), ('w_up2', vp), ('w_wino', vp), ('fast_act', ctypes.c_int32), ('in_add', vp), ('w_bf16s', vp),
+        ('w_f16', vp),
     ]
 
 
-ABI_VERSION = 106      # femasr_version(): femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* (femasr_conv_args ends with w_bf16s)
+ABI_VERSION = 107      # femasr_version(): femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -107,6 +108,8 @@ SIGNATURES = {
     'femasr_repack_oihw_up2': (c_int, [vp, vp, c_int, c_int, vp]),
     'femasr_packed_weight_bf16x3_bytes': (szt, [c_int, c_int, c_int, c_int]),
     'femasr_repack_oihw_bf16x3': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
+    'femasr_packed_weight_f16_bytes': (szt, [c_int, c_int, c_int, c_int]),
+    'femasr_repack_oihw_f16': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
     'femasr_set_decoder_math': (c_int, [vp, c_int]),
     'femasr_set_linear_math': (c_int, [vp, c_int]),
     'femasr_packed_weight_bf16s_bytes': (szt, [c_int, c_int]),

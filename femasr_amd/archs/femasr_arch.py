@@ -223,7 +223,10 @@ class FeMaSRNet(nn.Module):
         # 'fp32_strict': the same with the IEEE-exact SiLU - bit-identical to the oracle (OracleNet())
         # 'fp32_direct': every conv in the direct form - bit-identical to OracleNet(winograd=False)
         # 'bf16x3': the convs behind the lookup on the bf16 matrix cores with a 3-term hi/lo split (within the 1e-3 bound)
+        # 'fp16': the same convs on the fp16 matrix cores in ONE pass - the fast mode.  VQ indices identical to every other mode; the image
+        #   is half-precision grade (about 5e-4 of its range from the fp32 image), NOT within the 1e-3 bound of the modes above
         self.decoder_math = ignore_kwargs.get('decoder_math', 'fp32')       # (an extension key of this build in `network_g`)
+        self._check_decoder_math()
         # arithmetic of the 1x1 convs / nn.Linear layers (Swin qkv / proj / fc1 / fc2, before_quant):
         # 'bf16_split' (default): fp32-grade product on the bf16 matrix pipe - operands split exactly into three bf16 terms, six partial
         #   products, fp32 accumulation; ~3x closer to fp64 than the fp32 chain, bit-identical to OracleNet() (csrc/kernels_gemm_bf16.hip)
@@ -239,6 +242,12 @@ class FeMaSRNet(nn.Module):
         self._graphs = {}
         self._profile_on = False        # what enable_profile() last set on the live handle (a new handle starts with it off)
         self.debug_wino_limits = None   # tests only: (log2_total, log2_image) for this net's planner (include/femasr_hip_debug.h)
+
+    DECODER_MATH = {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3, 'fp16': 4}      # femasr_set_decoder_math
+
+    def _check_decoder_math(self):
+        if self.decoder_math not in self.DECODER_MATH:
+            raise ValueError(f"decoder_math must be 'fp32', 'fp32_strict', 'fp32_direct', 'bf16x3' or 'fp16', got {self.decoder_math!r}")
 
     # ------------------------------------------------------------------ weight change tracking
     # The native handle holds REPACKED COPIES of the weights.  Changes made through the nn.Module API are seen
@@ -310,13 +319,12 @@ class FeMaSRNet(nn.Module):
             self._version_sum = self._param_stamp()
             self._weights_dirty = False
         if self._streams_set != (self._handle.value, self.num_streams, self.decoder_math, self.linear_math, self.debug_wino_limits):
-            if self.decoder_math not in ('fp32', 'bf16x3', 'fp32_direct', 'fp32_strict'):
-                raise ValueError(f"decoder_math must be 'fp32', 'fp32_strict', 'fp32_direct' or 'bf16x3', got {self.decoder_math!r}")
+            self._check_decoder_math()
             if self.linear_math not in ('fp32', 'bf16_split'):
                 raise ValueError(f"linear_math must be 'bf16_split' or 'fp32', got {self.linear_math!r}")
             _lib.check(lib.femasr_set_linear_math(self._handle, {'fp32': 0, 'bf16_split': 1}[self.linear_math]))
             _lib.check(lib.femasr_set_streams(self._handle, int(self.num_streams)))
-            _lib.check(lib.femasr_set_decoder_math(self._handle, {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3}[self.decoder_math]))
+            _lib.check(lib.femasr_set_decoder_math(self._handle, self.DECODER_MATH[self.decoder_math]))
             lim = (0, 0) if self.debug_wino_limits is None else self.debug_wino_limits      # (0, 0): the handle's defaults again
             _lib.check(lib.femasr_debug_set_wino_limits(self._handle, int(lim[0]), int(lim[1])))
             self._streams_set = (self._handle.value, self.num_streams, self.decoder_math, self.linear_math, self.debug_wino_limits)

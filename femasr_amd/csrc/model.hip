@@ -83,6 +83,7 @@ struct WSpec {
     float *up2w = nullptr;  // phase matrices of a nearest-x2 conv (femasr_repack_oihw_up2; CONV_DIRECT on the halo kernels)
     void *bf16x3 = nullptr; // bf16x3 hi/lo fragments (CONV_BF16X3)
     float *wino = nullptr;  // Winograd-domain weights (CONV_WINO / CONV_WINO_UP2)
+    void *f16 = nullptr;    // fp16 fragments (CONV_F16): built only once the handle has selected decoder_math 4 (femasr_set_decoder_math)
     void *bf16s = nullptr;  // three bf16 planes of the (K x Cout) matrix (CONV_SPLIT: femasr_repack_k1_bf16s / femasr_repack_oihw_bf16s)
     bool up2 = false;       // the conv behind nn.Upsample(x2) of an up / decoder block
     bool set = false;
@@ -182,6 +183,7 @@ struct femasr_handle {
     float *cbT[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr}, *ee[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr};
     void *vq_aux[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr};       // bf16 codebook image of the two-pass search
     bool finalized = false;
+    bool f16_images = false;        // decoder_math 4 has been selected once: the CONV_F16 layers keep an fp16 weight image from then on
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -345,12 +347,15 @@ int build_specs(femasr_handle *h)
 // ---------------------------------------------------------------- conv forms
 // The form a conv runs in, decided here and nowhere else: from the modes, the layer's key and the shape-only conv arguments, never
 // from a pointer, so the dry run that sizes the workspace and the real run pick the same form, the decoder schedules its skip adds by
-// it (run_tail) and femasr_set_weight packs the weights of every form it can pick (layer_forms).  Precedence: bf16x3, Winograd, split
-// 3x3, split 1x1, direct.  The size limits inside the eligibility helpers only ever send a layer to the direct form.
+// it (run_tail) and femasr_set_weight packs the weights of every form it can pick (layer_forms).  Precedence: bf16x3 / fp16
+// (one mode each), Winograd, split 3x3, split 1x1, direct.  The size limits inside the eligibility helpers only ever send a layer to the direct form.
 ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string &key, const femasr_conv_args &a)
 {
     const bool behind = behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, key);
     if (behind && m.decoder_math == 1 && a.Cout > 4 && femasr_conv_bf16x3_shape_ok(&a)) return CONV_BF16X3;   // out_conv: exact VALU kernel in every mode
+    // decoder_math 4 = 'fp16': the same layers, by the same rule, in the one-pass fp16 form; a layer outside the rule falls through to
+    // what it takes in 'fp32_direct'
+    if (behind && m.decoder_math == 4 && a.Cout > 4 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
     // exact-fp32 mode: convs behind every codebook lookup run in the Winograd F(4x4,3x3) form, the x2 convs in the 25-product form
     // (they cannot move a VQ index; oracle: OracleNet.wino).  decoder_math 2 = 'fp32_direct' keeps the direct form; 0 runs the
     // SiLU of their GroupNorm prologue on the hardware exp2 / rcp units, 3 = 'fp32_strict' keeps it IEEE-exact (== oracle).
@@ -377,7 +382,8 @@ int gn_tiles(ConvForm f, const femasr_conv_args &a)
     const bool fusable = femasr_gn_fusable(a.Cout);
     switch (f) {
     case CONV_SPLIT: return 0;
-    case CONV_BF16X3: return fusable && a.Cout <= 256 ? ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16) : 0;       // <= 8 channels per group
+    case CONV_BF16X3:
+    case CONV_F16: return fusable && a.Cout <= 256 ? ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16) : 0;       // <= 8 channels per group
     case CONV_WINO:
     case CONV_WINO_UP2: return femasr_conv_halo_eligible(&a) && fusable ? femasr_conv_wino_gn_tiles(a.Ho, a.Wo) : 0;      // per 16x16-pixel sub-block
     default:       // halo kernels: per 8x16 tile; an x2 conv (phase filters) per half-resolution tile and phase
@@ -399,6 +405,20 @@ std::array<bool, CONV_FORM_COUNT> layer_forms(const femasr_handle *h, const WSpe
     for (m.decoder_math = 0; m.decoder_math <= 3; ++m.decoder_math)
         for (m.linear_math = 0; m.linear_math <= 1; ++m.linear_math) can[conv_form(h, m, w.key, a)] = true;
     return can;
+}
+
+// Does the layer run in the fp16 form under decoder_math 4?  Kept out of layer_forms on purpose: a handle that never selects the mode
+// allocates and packs nothing for it (femasr_set_decoder_math builds the images on the first selection, femasr_set_weight keeps them
+// current from then on).
+bool layer_takes_f16(const femasr_handle *h, const WSpec &w)
+{
+    if (w.kind != W_CONV || w.shape[2] != 3) return false;
+    femasr_conv_args a{};
+    a.B = 1; a.H = 16; a.W = 16; a.Cin = (int)w.shape[1]; a.Cout = (int)w.shape[0];
+    a.ksz = 3; a.stride = 1; a.pad = 1; a.up2 = w.up2;
+    ConvModes m;
+    m.decoder_math = 4;
+    return conv_form(h, m, w.key, a) == CONV_F16;
 }
 
 // ---------------------------------------------------------------- forward-time helpers
@@ -478,6 +498,7 @@ struct Ctx {
         const void *image = a.w;
         switch (f) {
         case CONV_BF16X3: image = a.w_bf16x3 = w->bf16x3; break;
+        case CONV_F16: image = a.w_f16 = w->f16; break;
         case CONV_WINO:
         case CONV_WINO_UP2: image = a.w_wino = w->wino; a.fast_act = h->modes.decoder_math == 0 ? 1 : 0; break;
         case CONV_SPLIT: image = a.w_bf16s = w->bf16s; break;
@@ -869,7 +890,7 @@ int check_ready(const femasr_handle *h)
 extern "C" {
 
 const char *femasr_last_error(void) { return g_err; }
-int femasr_version(void) { return 106; }
+int femasr_version(void) { return 107; }
 
 int femasr_create(const femasr_config *cfg, femasr_handle **out)
 {
@@ -913,7 +934,7 @@ void femasr_destroy(femasr_handle *h)
 {
     if (!h) return;
     for (auto &w : h->specs)
-        for (void *p : {(void *)w.dev, (void *)w.up2w, w.bf16x3, (void *)w.wino, w.bf16s}) if (p) (void)hipFree(p);
+        for (void *p : {(void *)w.dev, (void *)w.up2w, w.bf16x3, (void *)w.wino, w.bf16s, w.f16}) if (p) (void)hipFree(p);
     for (int q = 0; q < FEMASR_MAX_CODEBOOKS; ++q) {
         if (h->cbT[q]) (void)hipFree(h->cbT[q]);
         if (h->ee[q]) (void)hipFree(h->ee[q]);
@@ -968,6 +989,10 @@ int femasr_set_weight(femasr_handle *h, const char *key, const float *dev_ptr, c
         if (!rc && can[CONV_BF16X3]) {
             if (!w.bf16x3) FEMASR_CHECK_HIP(hipMalloc(&w.bf16x3, femasr_packed_weight_bf16x3_bytes(O, I, 3, 3)));
             rc = femasr_repack_oihw_bf16x3(nullptr, dev_ptr, O, I, 3, 3, w.bf16x3);
+        }
+        if (!rc && h->f16_images && layer_takes_f16(h, w)) {       // only once the fp16 mode has been selected
+            if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, femasr_packed_weight_f16_bytes(O, I, 3, 3)));
+            rc = femasr_repack_oihw_f16(nullptr, dev_ptr, O, I, 3, 3, w.f16);
         }
         if (!rc && (can[CONV_WINO] || can[CONV_WINO_UP2])) {
             if (!w.wino) FEMASR_CHECK_HIP(hipMalloc((void **)&w.wino, (w.up2 ? femasr_wino_up2_weight_floats(O, I) : femasr_wino_weight_floats(O, I)) * sizeof(float)));
@@ -1209,7 +1234,21 @@ int femasr_decode_indices(femasr_handle *h, void *stream, const int64_t *indices
 
 int femasr_set_decoder_math(femasr_handle *h, int mode)
 {
-    FEMASR_REQUIRE(h && mode >= 0 && mode <= 3, "set_decoder_math: mode must be 0 (fp32), 1 (bf16x3), 2 (fp32, direct convs only) or 3 (fp32, exact SiLU)");
+    FEMASR_REQUIRE(h && mode >= 0 && mode <= 4, "set_decoder_math: mode must be 0 (fp32), 1 (bf16x3), 2 (fp32, direct convs only), 3 (fp32, exact SiLU) or 4 (fp16)");
+    if (mode == 4 && !h->f16_images) {
+        // first selection: the fp16 images of the weights set so far, from their fragment-major fp32 images (the same values in the same
+        // K order as the OIHW tensors, which the handle does not keep); femasr_set_weight maintains them from now on
+        DeviceGuard guard(h->cfg.device);
+        FEMASR_REQUIRE(guard.ok, "set_decoder_math: hipSetDevice(%d) failed", h->cfg.device);
+        for (auto &w : h->specs) {
+            if (!w.set || !layer_takes_f16(h, w)) continue;
+            const int O = (int)w.shape[0], I = (int)w.shape[1];
+            if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, femasr_packed_weight_f16_bytes(O, I, 3, 3)));
+            FEMASR_CHECK(femasr_repack_packed_f16(nullptr, w.dev, O, I, w.f16));
+        }
+        FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
+        h->f16_images = true;
+    }
     if (h->modes.decoder_math != mode) h->plans.clear();
     h->modes.decoder_math = mode;
     return FEMASR_OK;

@@ -40,8 +40,8 @@ def build_parser():
     ap.add_argument('--tile_size', type=int, default=240)
     ap.add_argument('--tile_pad', type=int, default=16)
     ap.add_argument('--streams', type=int, default=3, help='sub-batch streams inside one batched forward of the tiled branch (3 measured fastest on MI355X)')
-    ap.add_argument('--decoder-math', choices=['fp32', 'fp32_strict', 'fp32_direct', 'bf16x3'], default='fp32',
-                    help="arithmetic of the convs behind the codebook lookup (FeMaSRNet.decoder_math); 'fp32_strict' is bit-identical to the CPU oracle")
+    ap.add_argument('--decoder-math', choices=['fp32', 'fp32_strict', 'fp32_direct', 'bf16x3', 'fp16'], default='fp32',
+                    help="arithmetic of the convs behind the codebook lookup (FeMaSRNet.decoder_math); 'fp32_strict' is bit-identical to the CPU oracle; 'fp16' is the fast half-precision mode (same VQ indices, image ~5e-4 of its range off)")
     ap.add_argument('--blend', action='store_true',
                     help='tiled branch: blend the overlapping tile halos instead of discarding them (no seams between tiles; NOT the '
                          "reference's arithmetic, off by default; needs 2 * tile_pad <= tile_size)")

@@ -59,7 +59,7 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  106: femasr_blend_tiles / femasr_blend_tiles_u8 (the opt-in overlap-blend paste).  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  107: femasr_conv_args ends with w_f16; femasr_repack_oihw_f16 / femasr_packed_weight_f16_bytes; femasr_set_decoder_math takes 4 ('fp16').  106: femasr_blend_tiles / femasr_blend_tiles_u8 (the opt-in overlap-blend paste).  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -205,11 +205,24 @@ typedef struct {
                              partial products of relative size >= 2^-16 accumulated in fp32 (two accumulators), ~3x closer to the fp64
                              result than the fp32 fmaf chain and bit-identical to oracle/femasr_oracle.c orc_linear_bf16s, which restates
                              the instruction's accumulation arithmetic from hardware probes (kernels_gemm_bf16.hip).  `w` is not read. */
+    const void *w_f16;    /* optional (struct version 107): femasr_repack_oihw_f16 weights.  When non-NULL the layer - under the shape and size
+                             rule of w_bf16x3: 3x3 stride-1 pad-1, Cin % 32 == 0, no LN prologue / activation, no prologue with up2 - runs on
+                             the fp16 matrix cores in ONE pass (HALF-precision grade, NOT within the 1e-3 bound of the other forms):
+                               t   = the activated input in fp32 (GroupNorm apply + SiLU on the hardware exp2 / rcp units as in the
+                                     w_bf16x3 prologue, nearest-x2 folded in, zero outside the image)
+                               t16 = fp16_rne(clamp(t, +-65504))      (a finite input never becomes Inf)
+                               w16 = fp16_rne(w), packed once; fp16 subnormals of either operand take part with their value
+                               out = bias + residuals + sum_k t16_k * w16_k: products exact in fp32 (11 + 11 bits), accumulated in fp32
+                                     by v_mfma_f32_32x32x16_f16; bias and residuals added in fp32; the output is stored as fp32.
+                             Every output element is within 128 * 2^-24 * sum_k |t16_k w16_k| of conv(t16, w16) evaluated exactly, plus
+                             the fp32 roundings of bias / residuals and, with the prologue, one fp16 ulp of t_k times |w16_k| wherever the
+                             SiLU's 8 fp32 ulp straddle an fp16 rounding boundary (tests/test_gpu_decoder_fp16.py).  gn_part as for
+                             w_bf16x3 (Cout / 32 a power of two <= 8).  `w` is not read. */
 } femasr_conv_args;
 /* Size limits (each a shape rule evaluated before any launch; DESIGN.md 5.7, tests/test_gpu_product_anchor.py):
  *   rows B*Ho*Wo < 2^31 - 256 for every form, else FEMASR_ERR_INVALID;
  *   w_wino: < 2^31 elements per tensor and < 2^27 per image (32-bit byte offsets), else FEMASR_ERR_INVALID;
- *   w_bf16x3: B*H*W*Cin < 2^31 and B*Ho*Wo*Cout < 2^31 (tests/test_gpu_mode_anchor.py), the 3x3 form of w_bf16s: B*H*W*Cin < 2^31,
+ *   w_bf16x3 and w_f16: B*H*W*Cin < 2^31 and B*Ho*Wo*Cout < 2^31 (tests/test_gpu_mode_anchor.py), the 3x3 form of w_bf16s: B*H*W*Cin < 2^31,
  *   else FEMASR_ERR_INVALID;
  *   the direct form (none of those weights given): the 3x3 stride-1 halo kernels and the Cout = 3 kernel hold the input patch
  *   offset as a 32-bit ELEMENT offset and are used while B*H*W*Cin < 2^31; a larger input - 2^32 elements and more included - runs
@@ -352,6 +365,9 @@ int femasr_set_linear_math(femasr_handle *h, int mode);
 /* Split-bf16 (hi/lo) fragment-major weights for the opt-in bf16x3 conv path (3x3 convs behind the VQ lookup). */
 size_t femasr_packed_weight_bf16x3_bytes(int O, int I, int kh, int kw);
 int femasr_repack_oihw_bf16x3(void *stream, const float *in, int O, int I, int kh, int kw, void *out);
+/* fp16 (round to nearest even) fragment-major weights for the opt-in one-pass fp16 conv path (femasr_conv_args.w_f16); I % 32 == 0. */
+size_t femasr_packed_weight_f16_bytes(int O, int I, int kh, int kw);
+int femasr_repack_oihw_f16(void *stream, const float *in, int O, int I, int kh, int kw, void *out);
 /* 0 (default, 'fp32'): every layer fp32; in single-codebook networks the 3x3 convs that do NOT feed the codebook lookup
  *    (after_quant, DecoderBlocks, the LQ encoder's two up-blocks) run in the Winograd F(4x4,3x3) form (4x fewer multiplies)
  *    with the GroupNorm+SiLU prologue on the hardware exp2 / rcp units (femasr_conv_args.fast_act): same fp32 accuracy against
@@ -360,7 +376,12 @@ int femasr_repack_oihw_bf16x3(void *stream, const float *in, int O, int I, int k
  * 3 ('fp32_strict'): the same with the IEEE-exact SiLU: bit-identical to the oracle (OracleNet()).
  * 1: those convs (and the x2 convs) use the bf16x3 path instead: output within the north-star 1e-3 bound of the fp32 result
  *    (measured ~1e-4).
- * 2 ('fp32_direct'): fp32 with every conv in the direct form, bit-identical to OracleNet(winograd=False). */
+ * 2 ('fp32_direct'): fp32 with every conv in the direct form, bit-identical to OracleNet(winograd=False).
+ * 4 ('fp16'): the convs that mode 1 sends to the bf16x3 path (behind every lookup, Cout > 4, the w_bf16x3 shape rule) run in the one-pass
+ *    fp16 form of femasr_conv_args.w_f16 instead; every other layer runs as in mode 2 (out_conv: the exact VALU kernel).  VQ indices
+ *    are bit-identical to every other mode (nothing in front of a lookup changes); the IMAGE is half-precision grade, about 5e-4 of the
+ *    output range from the fp32 image - NOT within the 1e-3 bound of modes 0-3.  The fp16 weight images are built when the mode is first
+ *    selected and rebuilt by femasr_set_weight from then on; a handle that never selects it allocates nothing for it. */
 int femasr_set_decoder_math(femasr_handle *h, int mode);
 
 /* ---- image pre / post-processing (the steps either side of the path) ---- */
