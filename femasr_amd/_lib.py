@@ -137,6 +137,9 @@ SIGNATURES = {
     'femasr_niqe_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
     'femasr_niqe_plane_offsets': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(szt * 4)]),
     'femasr_niqe_features': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, c_int, vp, vp, vp, szt]),
+    'femasr_color_fix_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_color_fix': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, szt]),
+    'femasr_color_fix_u8': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp, szt]),
     'femasr_clock_probe': (c_int, [vp, c_int, vp]),
     'femasr_clock_probe_entries': (c_int, []),
 }

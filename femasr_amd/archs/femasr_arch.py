@@ -241,6 +241,10 @@ class FeMaSRNet(nn.Module):
         self.use_graph = False
         self._graphs = {}
         self._profile_on = False        # what enable_profile() last set on the live handle (a new handle starts with it off)
+        # levels of the opt-in wavelet colour fix (`color_fix=True` on test / test_u8 / test_tile / test_tile_u8; femasr_amd/colorfix.py,
+        # DESIGN.md 16): the blur that separates "coarse" (taken from the upsampled input) from "detail" (the network's) reaches 2^levels - 1
+        # pixels to either side
+        self.color_fix_levels = 5
         self.debug_wino_limits = None   # tests only: (log2_total, log2_image) for this net's planner (include/femasr_hip_debug.h)
 
     DECODER_MATH = {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3, 'fp16': 4}      # femasr_set_decoder_math
@@ -459,18 +463,27 @@ class FeMaSRNet(nn.Module):
         return out, idx
 
     @torch.no_grad()
-    def test_u8(self, img_u8, bgr=False, out=None):
+    def test_u8(self, img_u8, bgr=False, out=None, color_fix=False):
         """The CLI arithmetic of inference_femasr.py:50-67 on the device in ONE native call: uint8 (H,W,3) or (B,H,W,3) image(s) ->
         uint8 (sH,sW,3) / (B,sH,sW,3); decode (`/255.`) is fused into the forward's mirror-pad kernel and tensor2img (clamp, x255,
         round half to even) into its crop kernel (femasr_forward_u8) - the same bits as imgproc.u8_to_input -> test() ->
         imgproc.output_to_u8, without the two fp32 NCHW images in between.  `out`: a contiguous uint8 (B,sH,sW,3) tensor the crop
-        kernel stores into (the tiled / multi-GPU callers pass slices of their result or all-gather send buffers)."""
+        kernel stores into (the tiled / multi-GPU callers pass slices of their result or all-gather send buffers).
+        color_fix=True (NOT the reference's arithmetic, off by default): the wavelet colour fix of the result's BYTES against the input's
+        (femasr_amd.colorfix.wavelet_color_fix, `color_fix_levels` levels), in place on the result."""
         if img_u8.device.type != 'cuda':
             raise _lib.FemasrError('test_u8: tensor must be on the GPU (no CPU fallback)')
         x, single = self._u8_batch(img_u8)
         lib, h = self._native(x.device)
         out = self._forward_native(lib, h, _U8, x, 1, out, flags=(int(bool(bgr)),), indices=False)[0]
+        if color_fix:
+            self._color_fix(out, x)
         return out[0] if single else out
+
+    def _color_fix(self, canvas, x):
+        """The opt-in wavelet colour fix of a finished result against the whole input, in place (femasr_amd/colorfix.py)."""
+        from ..colorfix import wavelet_color_fix
+        return wavelet_color_fix(canvas, x, self.color_fix_levels, out=canvas)
 
     @staticmethod
     def _u8_batch(img_u8):
@@ -500,11 +513,17 @@ class FeMaSRNet(nn.Module):
         return self.encode_and_decode(input, gt_indices)
 
     @torch.no_grad()
-    def test(self, input, out=None):
+    def test(self, input, out=None, color_fix=False):
         """femasr_arch.py:449-468: mirror-pad to (h//wsz+1)*wsz, run, crop to (h*s, w*s).  `out` (not in the reference): a
         contiguous float32 (B, 3, h*s, w*s) tensor the result is written INTO by the last kernel of the forward - the tiled /
-        multi-GPU callers pass slices of their result or all-gather send buffers, so no copy follows."""
-        return self._run(input, 1, out)[0]
+        multi-GPU callers pass slices of their result or all-gather send buffers, so no copy follows.
+        color_fix=True (not in the reference, off by default): the wavelet colour fix of the result against `input`
+        (femasr_amd.colorfix.wavelet_color_fix, `color_fix_levels` levels), after the forward - outside the captured graph with
+        `use_graph` - and in place on the result."""
+        y = self._run(input, 1, out)[0]
+        if color_fix:
+            self._color_fix(y, input.detach().to(torch.float32).contiguous())
+        return y
 
     @torch.no_grad()
     def test_with_indices(self, input):
@@ -531,7 +550,7 @@ class FeMaSRNet(nn.Module):
 
     # ------------------------------------------------------------------ tiled inference
     @torch.no_grad()
-    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False):
+    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False, color_fix=False):
         """Reference semantics of femasr_arch.py:387-447 (overlap-discard paste onto a zero canvas), but
         tiles of one shape class run as batched `test()` calls, and with world_size > 1 each rank
         computes a contiguous share of every class; `gather(results, classes, batch, channel, scale) -> list per rank`
@@ -541,11 +560,16 @@ class FeMaSRNet(nn.Module):
         blend=True (NOT the reference's arithmetic, hence off by default): instead of discarding the halos, every canvas pixel is the
         weighted mean of the upscaled windows that contain it (linear ramps across the overlaps: tiling.blend_weight_1d)
         - no seams where neighbouring bodies meet.  The tiles, their batching and the collective are the same; only the last step
-        differs (ONE femasr_blend_tiles launch instead of the per-class pastes).  Needs 2 * tile_pad <= tile_size (ValueError)."""
-        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste, blend)
+        differs (ONE femasr_blend_tiles launch instead of the per-class pastes).  Needs 2 * tile_pad <= tile_size (ValueError).
+        color_fix=True (NOT the reference's arithmetic either, off by default): after the paste or the blend, on the pasting ranks, the
+        wavelet colour fix of the WHOLE canvas against the WHOLE input (femasr_amd/colorfix.py): everything coarser than
+        ~2^color_fix_levels pixels comes from the bicubically upsampled input, which knows nothing of tiles - the per-tile tone offsets
+        that `blend` only turns into ramps go away.  Defined on canvas and input alone, so independent of the partition and the ranks."""
+        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste, blend, color_fix)
 
     @torch.no_grad()
-    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False, blend=False):
+    def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False, blend=False,
+                     color_fix=False):
         """`test_tile` on uint8 images end to end (round 6; the CLI's tiled branch, inference_femasr.py:58-67 with femasr_arch.py:387-447):
         uint8 (H,W,3) / (B,H,W,3) in -> uint8 (sH,sW,3) / (B,sH,sW,3) out.  Tiles are cropped as uint8, every batched call is ONE
         `test_u8` (decode fused into the mirror-pad kernel, tensor2img into the crop kernel, which stores straight into the result /
@@ -553,12 +577,15 @@ class FeMaSRNet(nn.Module):
         traffic; no 805-MB fp32 canvas at 8192^2).  Bit-identical to output_to_u8(test_tile(u8_to_input(img))): tensor2img is
         element-wise and every output pixel comes from exactly one tile.
         blend=True: as in `test_tile`, on the BYTES the tiles hold after tensor2img (the all-gather payload stays one byte per value):
-        the weighted mean of the covering windows' bytes, rounded half to even - not tensor2img of the fp32 blend."""
+        the weighted mean of the covering windows' bytes, rounded half to even - not tensor2img of the fp32 blend.
+        color_fix=True: as in `test_tile`, on the canvas BYTES against the input bytes (planes byte / 255, the result rounded half to even):
+        no fp32 canvas is held, the fix works through the planes in groups of bounded size."""
         x, single = self._u8_batch(img_u8)
-        output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste, blend)
+        output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste, blend,
+                             color_fix)
         return output[0] if single and output is not None else output
 
-    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste, blend=False):
+    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste, blend=False, color_fix=False):
         """The tile schedule of `test_tile` and `test_tile_u8`: `x` is the contiguous image batch in tile format `fmt`,
         `run(crops[, out=])` the batched call on the crops of one shape class.  Returns the canvas (None with paste=False)."""
         if blend:
@@ -610,6 +637,8 @@ class FeMaSRNet(nn.Module):
                 for hw, tl in owned_all[r].items():
                     if tl:
                         self._paste_tiles(fmt, output, res[hw], tl, batch, s)
+        if color_fix and output is not None:
+            self._color_fix(output, x)                  # (the one post-paste step: whole canvas against whole input; counted as 'paste')
         if ev:
             ev[3].record()
             self._split_events = (ev, sum(len(tl) for tl in mine.values()))

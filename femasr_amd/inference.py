@@ -45,6 +45,10 @@ def build_parser():
     ap.add_argument('--blend', action='store_true',
                     help='tiled branch: blend the overlapping tile halos instead of discarding them (no seams between tiles; NOT the '
                          "reference's arithmetic, off by default; needs 2 * tile_pad <= tile_size)")
+    ap.add_argument('--color-fix', action='store_true',
+                    help='wavelet colour fix of the result: detail from the network, everything coarser than ~2^N pixels from the bicubically '
+                         "upsampled input (removes per-tile tone offsets and colour drift; NOT the reference's arithmetic, off by default)")
+    ap.add_argument('--color-fix-levels', type=int, default=5, metavar='N', help='levels of --color-fix (1..12, default 5)')
     return ap
 
 
@@ -71,6 +75,10 @@ def main(argv=None):
     else:
         raise SystemExit('no network here: pass -w <weights.pth> (FeMaSR_SRX4/SRX2_model_g.pth) or --synthetic-seed N')
     model.decoder_math = args.decoder_math
+    if not 1 <= args.color_fix_levels <= 12:
+        raise SystemExit(f'--color-fix-levels must be in 1..12, got {args.color_fix_levels}')
+    model.color_fix_levels = args.color_fix_levels
+    fix = {'color_fix': True} if args.color_fix else {}
     model.num_streams = args.streams          # tiled images run as batched test() calls: sub-batches on internal streams (bit-identical for any split)
     model = model.to(dev).eval()
 
@@ -84,14 +92,14 @@ def main(argv=None):
         h, w = rgb.shape[:2]
         if h * w < args.max_size ** 2:
             # whole image: ONE native call, uint8 in -> uint8 out (decode fused into the pad kernel, tensor2img into the crop kernel)
-            u8 = model.test_u8(xu8) if rank == 0 else None
+            u8 = model.test_u8(xu8, **fix) if rank == 0 else None
         else:
             # tiled: uint8 tiles in, uint8 tiles out - crops, the all-gather over xGMI and the paste move one byte per value, no fp32 image
             # or canvas is ever held (FeMaSRNet.test_tile_u8); with several ranks only rank 0 pastes
             if world > 1:
-                u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend)
+                u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend, **fix)
             else:
-                u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend)
+                u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend, **fix)
         if rank == 0:
             Image.fromarray(u8.cpu().numpy(), 'RGB').save(os.path.join(args.output, img_name))
     if world > 1:

@@ -350,11 +350,18 @@ class FeMaSRModel:
         min_size = 8000 * 8000
         _, _, h, w = self.lq.shape
         # `val: tile_blend: true` (an extension key, absent = false): the tiled branch blends the tile overlaps (FeMaSRNet.test_tile)
-        blend = bool((self.opt.get('val') or {}).get('tile_blend', False))
+        val = self.opt.get('val') or {}
+        blend = bool(val.get('tile_blend', False))
+        # `val: color_fix: true` (an extension key, absent = false): the opt-in wavelet colour fix on either branch; `val: color_fix_levels: N`
+        # sets the network's `color_fix_levels` (absent: the network keeps its own, 5)
+        kw = {'blend': True} if blend else {}
+        fix = {'color_fix': True} if val.get('color_fix', False) else {}
+        if fix and val.get('color_fix_levels') is not None:
+            self.net_g.color_fix_levels = int(val['color_fix_levels'])
         if h * w < min_size:
-            self.output = self.net_g.test(self.lq)
+            self.output = self.net_g.test(self.lq, **fix)
         else:
-            self.output = self.net_g.test_tile(self.lq, blend=True) if blend else self.net_g.test_tile(self.lq)
+            self.output = self.net_g.test_tile(self.lq, **kw, **fix)
 
     @torch.no_grad()
     def extract_gt_indices(self, gt=None):

@@ -479,6 +479,30 @@ int femasr_niqe_features(void *stream, const uint8_t *img, int B, int H, int W, 
                          const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w, int taps_w,
                          double *features, int32_t *positions, void *ws, size_t ws_bytes);
 
+/* ---- wavelet colour fix (opt-in, femasr_amd.colorfix / FeMaSRNet.test*(..., color_fix=True); NOT the reference's arithmetic) ----
+ * The coarse bands of a super-resolved canvas are taken from its bicubically upsampled input:
+ *   up = imresize(lq, s) (femasr_imresize's float32 result);  d = up - sr;  for i = 0 .. levels-1, r = 2^i, indices clamped to the plane:
+ *   t[y,x] = (d[y,cl(x-r)]/4 + d[y,x]/2) + d[y,cl(x+r)]/4;  d'[y,x] = (t[cl(y-r),x]/4 + t[y,x]/2) + t[cl(y+r),x]/4;   out = sr + d.
+ * Every step after the resize is one IEEE fp32 operation in the order written (tests/colorfix_ref.py restates it bit for bit).
+ *   femasr_color_fix     sr, out: `planes` fp32 planes of (sH,sW) back to back ((B,C,sH,sW)); lq: as many planes of (H,W)
+ *   femasr_color_fix_u8  sr, out: B uint8 (sH,sW,3) images; lq: B uint8 (H,W,3) images.  Planes are (float)byte / 255.0f (IEEE division); the
+ *                        result is stored as rint(clamp(out, 0, 1) * 255), half to even (tensor2img's rounding).  It fixes the BYTES the
+ *                        canvas holds, it is not the quantised fp32 fix.
+ * `out` may be `sr` (in place).  w_h, idx_h: (sH,taps_h) and w_w, idx_w: (sW,taps_w): femasr_imresize's DEVICE tables for scale s, no
+ * antialiasing.  `ws`: 256-byte aligned; femasr_color_fix_workspace_bytes(planes, ...) is what a group of `planes` planes needs (two fp32
+ * buffers of (planes,sH,sW) and the resize's fp64 intermediate (planes,sH,W)).  The call works through its planes in groups of as many
+ * planes as `ws_bytes` holds (a uint8 image is three planes: channel c of image b is plane 3 b + c), so a caller bounds the peak by sizing
+ * the workspace for fewer planes than it passes - down to one, also for uint8: no canvas is ever held in fp32.  levels + 3 launches per group on `stream`; no atomics, no allocation, no synchronisation (capture-safe).
+ * Refused with FEMASR_ERR_INVALID before any launch: a null pointer, a count or size <= 0, sH != s H or sW != s W, levels outside 1..12,
+ * a plane of 2^31 elements or more, a workspace smaller than one plane's or not 256-byte aligned. */
+int femasr_color_fix_workspace_bytes(int planes, int H, int W, int sH, int sW, int s, size_t *bytes);
+int femasr_color_fix(void *stream, const float *sr, const float *lq, int planes, int H, int W, int sH, int sW, int s, int levels,
+                     const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w, int taps_w, float *out,
+                     void *ws, size_t ws_bytes);
+int femasr_color_fix_u8(void *stream, const uint8_t *sr, const uint8_t *lq, int B, int H, int W, int sH, int sW, int s, int levels,
+                        const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w, int taps_w, uint8_t *out,
+                        void *ws, size_t ws_bytes);
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
