@@ -43,7 +43,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 107      # femasr_version(): femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
+ABI_VERSION = 107      # femasr_version(): (additive, number kept: femasr_repack_k1_f16, the ksz = 1 meaning of w_f16, linear_math 2) femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -110,6 +110,8 @@ SIGNATURES = {
     'femasr_repack_oihw_bf16x3': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
     'femasr_packed_weight_f16_bytes': (szt, [c_int, c_int, c_int, c_int]),
     'femasr_repack_oihw_f16': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
+    'femasr_packed_weight_k1_f16_bytes': (szt, [c_int, c_int]),
+    'femasr_repack_k1_f16': (c_int, [vp, vp, c_int, c_int, vp]),
     'femasr_set_decoder_math': (c_int, [vp, c_int]),
     'femasr_set_linear_math': (c_int, [vp, c_int]),
     'femasr_packed_weight_bf16s_bytes': (szt, [c_int, c_int]),

@@ -231,7 +231,13 @@ class FeMaSRNet(nn.Module):
         # 'bf16_split' (default): fp32-grade product on the bf16 matrix pipe - operands split exactly into three bf16 terms, six partial
         #   products, fp32 accumulation; ~3x closer to fp64 than the fp32 chain, bit-identical to OracleNet() (csrc/kernels_gemm_bf16.hip)
         # 'fp32': one fp32 fmaf chain per output on the fp32 MFMA - bit-identical to OracleNet(linear_math='fp32')
+        # 'fp16' (opt-in): the same layers - and the stride-1 3x3 convs in front of the lookup - in ONE fp16 pass: input and weight rounded once to
+        #   fp16, fp32 accumulation (csrc/kernels_gemm_f16.hip, kernels_conv_f16.hip).  The first mode in which VQ indices may DIFFER from the
+        #   other modes: a token whose two nearest codes are nearly tied can flip (0 - 2 % of the tokens on the test cases), the image changes by
+        #   up to ~0.1 of unit range where one does and is NOT within the 1e-3 bound anywhere.  Deterministic and bit-identical across
+        #   batch size, streams, graph replay and tiling within the mode.  With decoder_math='fp16' the whole network is half-precision grade
         self.linear_math = ignore_kwargs.get('linear_math', 'bf16_split')
+        self._check_linear_math()
         # True: each (shape, mode) class is captured once into a hipGraph (torch.cuda.CUDAGraph around femasr_forward, which
         # is capture-safe: no allocation / synchronisation inside) and replayed; inputs are copied into the graph's static
         # buffer and the outputs are copies of its static outputs.  Only pays when the ~330 launches are host-bound (tiny
@@ -252,6 +258,12 @@ class FeMaSRNet(nn.Module):
     def _check_decoder_math(self):
         if self.decoder_math not in self.DECODER_MATH:
             raise ValueError(f"decoder_math must be 'fp32', 'fp32_strict', 'fp32_direct', 'bf16x3' or 'fp16', got {self.decoder_math!r}")
+
+    LINEAR_MATH = {'fp32': 0, 'bf16_split': 1, 'fp16': 2}      # femasr_set_linear_math
+
+    def _check_linear_math(self):
+        if self.linear_math not in self.LINEAR_MATH:
+            raise ValueError(f"linear_math must be 'bf16_split', 'fp32' or 'fp16', got {self.linear_math!r}")
 
     # ------------------------------------------------------------------ weight change tracking
     # The native handle holds REPACKED COPIES of the weights.  Changes made through the nn.Module API are seen
@@ -324,9 +336,8 @@ class FeMaSRNet(nn.Module):
             self._weights_dirty = False
         if self._streams_set != (self._handle.value, self.num_streams, self.decoder_math, self.linear_math, self.debug_wino_limits):
             self._check_decoder_math()
-            if self.linear_math not in ('fp32', 'bf16_split'):
-                raise ValueError(f"linear_math must be 'bf16_split' or 'fp32', got {self.linear_math!r}")
-            _lib.check(lib.femasr_set_linear_math(self._handle, {'fp32': 0, 'bf16_split': 1}[self.linear_math]))
+            self._check_linear_math()
+            _lib.check(lib.femasr_set_linear_math(self._handle, self.LINEAR_MATH[self.linear_math]))
             _lib.check(lib.femasr_set_streams(self._handle, int(self.num_streams)))
             _lib.check(lib.femasr_set_decoder_math(self._handle, self.DECODER_MATH[self.decoder_math]))
             lim = (0, 0) if self.debug_wino_limits is None else self.debug_wino_limits      # (0, 0): the handle's defaults again

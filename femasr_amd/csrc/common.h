@@ -109,6 +109,15 @@ const char *femasr_conv_f16_variant_name(int v);
 // the fp16 image built from the layer's fragment-major fp32 image (femasr_repack_oihw of a 3x3 conv with I % 32 == 0) instead of the OIHW tensor
 int femasr_repack_packed_f16(hipStream_t stream, const float *packed, int O, int I, void *out);
 
+// one-pass fp16 GEMM of the 1x1 layers (kernels_gemm_f16.hip): the split GEMM's k1 layers and shape rule, linear_math 2
+bool femasr_gemm_f16_shape_ok(const femasr_conv_args *a);
+int femasr_gemm_f16_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
+int femasr_gemm_f16_variant_count();
+int femasr_gemm_f16_pick_variant(const femasr_conv_args *a);
+const char *femasr_gemm_f16_variant_name(int v);
+// the fp16 image built from the layer's GEMM-layout fp32 image (femasr_repack_oihw with kh = kw = 1) instead of the (out, in) tensor
+int femasr_repack_packed_k1_f16(hipStream_t stream, const float *packed, int O, int I, void *out);
+
 // The forms a conv runs in, in profile-slot order (femasr_create lays the slots out from this list)
 enum ConvForm {
     CONV_DIRECT,      // fp32 halo / implicit-GEMM kernels, the VALU out_conv kernel (kernels_conv.hip, kernels_gemm.hip)
@@ -116,7 +125,8 @@ enum ConvForm {
     CONV_WINO,        // Winograd F(4x4,3x3) (w_wino)
     CONV_WINO_UP2,    // the 25-product form of nearest-x2 + 3x3 conv (w_wino with up2)
     CONV_SPLIT,       // split-bf16 GEMM: 1x1 / linear layer, or 3x3 conv over K = 9 Cin (w_bf16s)
-    CONV_F16,         // one-pass fp16 halo kernels (w_f16); last, so the slots of the other forms keep their numbers
+    CONV_F16,         // one-pass fp16 halo kernels (w_f16 with ksz = 3)
+    CONV_GEMM_F16,    // one-pass fp16 GEMM of a 1x1 layer (w_f16 with ksz = 1); new forms go last, so the slots of the others keep their numbers
     CONV_FORM_COUNT
 };
 int femasr_conv_form_variant_count(ConvForm f);

@@ -1271,7 +1271,7 @@ int femasr_clock_probe(void *stream, int mfmas_per_wave, unsigned long long *tic
 int femasr_conv_form_variant_count(ConvForm f)
 {
     const int n[CONV_FORM_COUNT] = {femasr_conv_variant_count(), femasr_conv_bf16x3_variant_count(), femasr_conv_wino_variant_count(), 1,
-                                    femasr_gemm_bf16s_variant_count(), femasr_conv_f16_variant_count()};
+                                    femasr_gemm_bf16s_variant_count(), femasr_conv_f16_variant_count(), femasr_gemm_f16_variant_count()};
     return n[f];
 }
 
@@ -1283,6 +1283,7 @@ const char *femasr_conv_form_variant_name(ConvForm f, int v)
     case CONV_WINO_UP2: return femasr_conv_wino_up2_variant_name();
     case CONV_SPLIT: return femasr_gemm_bf16s_variant_name(v);
     case CONV_F16: return femasr_conv_f16_variant_name(v);
+    case CONV_GEMM_F16: return femasr_gemm_f16_variant_name(v);
     default: return femasr_conv_variant_name(v);
     }
 }
@@ -1296,6 +1297,7 @@ int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a
     case CONV_WINO_UP2: r = femasr_conv_wino_up2_launch(s, a, flops_out); break;
     case CONV_SPLIT: r = femasr_gemm_bf16s_launch(s, a, a->w_bf16s, &v, flops_out); break;
     case CONV_F16: r = femasr_conv_f16_launch(s, a, &v, flops_out); break;
+    case CONV_GEMM_F16: r = femasr_gemm_f16_launch(s, a, &v, flops_out); break;
     default: r = femasr_conv2d_launch(s, a, nullptr, &v, flops_out); break;
     }
     for (int g = 0; g < f; ++g) v += femasr_conv_form_variant_count((ConvForm)g);
@@ -1306,7 +1308,7 @@ int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a
 // femasr_conv2d: the form whose weights are given
 static ConvForm conv2d_form(const femasr_conv_args *a)
 {
-    return !a ? CONV_DIRECT : a->w_bf16s ? CONV_SPLIT : a->w_bf16x3 ? CONV_BF16X3 : a->w_f16 ? CONV_F16 : !a->w_wino ? CONV_DIRECT : a->up2 ? CONV_WINO_UP2 : CONV_WINO;
+    return !a ? CONV_DIRECT : a->w_bf16s ? CONV_SPLIT : a->w_bf16x3 ? CONV_BF16X3 : a->w_f16 ? (a->ksz == 1 ? CONV_GEMM_F16 : CONV_F16) : !a->w_wino ? CONV_DIRECT : a->up2 ? CONV_WINO_UP2 : CONV_WINO;
 }
 
 extern "C" int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *name, int cap)
@@ -1324,6 +1326,7 @@ extern "C" int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *n
     case CONV_WINO_UP2: v = 0; break;
     case CONV_SPLIT: v = femasr_gemm_bf16s_pick_variant(a); break;
     case CONV_F16: v = femasr_conv_f16_pick_variant(a); break;
+    case CONV_GEMM_F16: v = femasr_gemm_f16_pick_variant(a); break;
     default: v = femasr_conv2d_pick_variant(a); break;
     }
     const char *s = femasr_conv_form_variant_name(f, v);
@@ -1342,6 +1345,8 @@ extern "C" int femasr_conv2d(void *stream, const femasr_conv_args *a)
                    "conv2d: w_bf16s given but the layer is neither a 1x1 stride-1 layer nor a 3x3 pad-1 conv of stride 1 or 2, with Cin %% 64 == 0 and no prologue");
     FEMASR_REQUIRE(f != CONV_BF16X3 || femasr_conv_bf16x3_eligible(a), "conv2d: w_bf16x3 given but the layer is not eligible for the bf16x3 path");
     FEMASR_REQUIRE(f != CONV_F16 || femasr_conv_f16_eligible(a), "conv2d: w_f16 given but the layer is not eligible for the fp16 path (the bf16x3 shape rule)");
+    FEMASR_REQUIRE(f != CONV_GEMM_F16 || femasr_gemm_f16_shape_ok(a),
+                   "conv2d: w_f16 given with ksz = 1 but the layer is not a 1x1 stride-1 layer with Cin %% 64 == 0 and no prologue");
     FEMASR_REQUIRE(f != CONV_WINO_UP2 || femasr_conv_wino_up2_shape_ok(a),
                    "conv2d: w_wino given with up2 but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0, no prologue");
     FEMASR_REQUIRE(f != CONV_WINO || femasr_conv_wino_shape_ok(a), "conv2d: w_wino given but the layer is not a 3x3 stride-1 pad-1 conv with Cin %% 32 == 0, Cout %% 64 == 0");

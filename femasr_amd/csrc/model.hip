@@ -83,9 +83,11 @@ struct WSpec {
     float *up2w = nullptr;  // phase matrices of a nearest-x2 conv (femasr_repack_oihw_up2; CONV_DIRECT on the halo kernels)
     void *bf16x3 = nullptr; // bf16x3 hi/lo fragments (CONV_BF16X3)
     float *wino = nullptr;  // Winograd-domain weights (CONV_WINO / CONV_WINO_UP2)
-    void *f16 = nullptr;    // fp16 fragments (CONV_F16): built only once the handle has selected decoder_math 4 (femasr_set_decoder_math)
+    void *f16 = nullptr;    // fp16 fragments (CONV_F16 of a 3x3 conv, CONV_GEMM_F16 of a 1x1 layer): built only once the handle has selected a mode
+                            // that runs the layer in that form (decoder_math 4 / linear_math 2; layer_f16_image)
     void *bf16s = nullptr;  // three bf16 planes of the (K x Cout) matrix (CONV_SPLIT: femasr_repack_k1_bf16s / femasr_repack_oihw_bf16s)
     bool up2 = false;       // the conv behind nn.Upsample(x2) of an up / decoder block
+    int stride = 1;         // 2: a down conv of the encoder
     bool set = false;
     size_t numel() const { size_t n = 1; for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i]; return n; }
 };
@@ -168,7 +170,7 @@ struct ProfRec { int slot; hipEvent_t e0, e1; double flops, bytes; };
 
 struct ConvModes {          // the handle's settings that choose the form of a conv (conv_form)
     int decoder_math = 0;   // femasr_set_decoder_math
-    int linear_math = 1;    // femasr_set_linear_math: 1 = fp32-grade product on the bf16 matrix pipe, 0 = fp32 MFMA chain
+    int linear_math = 1;    // femasr_set_linear_math: 1 = fp32-grade product on the bf16 matrix pipe, 0 = fp32 MFMA chain, 2 = one fp16 pass
     int wino_log2_total = FEMASR_WINO_LOG2_TOTAL, wino_log2_image = FEMASR_WINO_LOG2_IMAGE;      // femasr_debug_set_wino_limits (planner only)
 };
 
@@ -184,6 +186,7 @@ struct femasr_handle {
     void *vq_aux[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr};       // bf16 codebook image of the two-pass search
     bool finalized = false;
     bool f16_images = false;        // decoder_math 4 has been selected once: the CONV_F16 layers keep an fp16 weight image from then on
+    bool f16_front_images = false;  // linear_math 2 has been selected once: the same for the layers that mode takes (in front of the lookup)
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -240,11 +243,11 @@ struct Scope {   // event pair around one launch (or a small group of launches)
     }
 };
 
-void add_conv(femasr_handle *h, const std::string &p, int cin, int cout, int k, bool up2 = false)
+void add_conv(femasr_handle *h, const std::string &p, int cin, int cout, int k, bool up2 = false, int stride = 1)
 {
     WSpec w; w.key = p + ".weight"; w.kind = W_CONV; w.ndim = 4;
     w.shape[0] = cout; w.shape[1] = cin; w.shape[2] = k; w.shape[3] = k;
-    w.up2 = up2;
+    w.up2 = up2; w.stride = stride;
     h->specs.push_back(w);
     WSpec b; b.key = p + ".bias"; b.kind = W_VEC; b.ndim = 1; b.shape[0] = cout;
     h->specs.push_back(b);
@@ -283,7 +286,7 @@ int build_specs(femasr_handle *h)
         const int ic = channels_at(res), oc = channels_at(res / 2);
         FEMASR_REQUIRE(ic > 0 && oc > 0, "unsupported resolution %d", res);
         const std::string p = enc + ".blocks." + std::to_string(bi);
-        add_conv(h, p + ".0", ic, oc, 3);
+        add_conv(h, p + ".0", ic, oc, 3, false, 2);
         add_resblock(h, p + ".1", oc);
         add_resblock(h, p + ".2", oc);
         res /= 2;
@@ -348,7 +351,7 @@ int build_specs(femasr_handle *h)
 // The form a conv runs in, decided here and nowhere else: from the modes, the layer's key and the shape-only conv arguments, never
 // from a pointer, so the dry run that sizes the workspace and the real run pick the same form, the decoder schedules its skip adds by
 // it (run_tail) and femasr_set_weight packs the weights of every form it can pick (layer_forms).  Precedence: bf16x3 / fp16
-// (one mode each), Winograd, split 3x3, split 1x1, direct.  The size limits inside the eligibility helpers only ever send a layer to the direct form.
+// (one mode each), Winograd, one-pass fp16 in front of the lookup (linear_math 2), split 3x3, split 1x1, direct.  The size limits inside the eligibility helpers only ever send a layer to the direct form.
 ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string &key, const femasr_conv_args &a)
 {
     const bool behind = behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, key);
@@ -363,14 +366,20 @@ ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string
         if (femasr_conv_wino_up2_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO_UP2;
         if (femasr_conv_wino_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO;
     }
-    if (m.linear_math == 1) {
+    if (m.linear_math >= 1) {
         // a 3x3 conv in FRONT of a lookup (encoder down convs and ResBlocks, the conv behind every RSTB) runs as the split-bf16 GEMM
         // over K = 9 Cin - the arithmetic of the linear layers (oracle: conv3x3_bf16s).  Its GroupNorm + SiLU prologue becomes a pass
         // of its own (the GEMM takes plain rows).
         femasr_conv_args plain = a;
         plain.prologue = FEMASR_PRO_NONE;
-        if (!behind && (a.prologue == FEMASR_PRO_NONE || a.prologue == FEMASR_PRO_GN_SILU) && femasr_conv3x3_bf16s_shape_ok(&plain)) return CONV_SPLIT;
-        if (a.ksz == 1 && femasr_gemm_bf16s_shape_ok(&a)) return CONV_SPLIT;
+        const bool split3 = !behind && (a.prologue == FEMASR_PRO_NONE || a.prologue == FEMASR_PRO_GN_SILU) && femasr_conv3x3_bf16s_shape_ok(&plain);
+        const bool split1 = a.ksz == 1 && femasr_gemm_bf16s_shape_ok(&a);
+        // linear_math 2 = 'fp16': exactly these layers, in ONE fp16 pass where the fp16 kernels' own shape rules hold - the stride-1 3x3 convs in
+        // the fp16 halo form (its fused GroupNorm + SiLU prologue and GroupNorm partials replace the stand-alone passes around the split form),
+        // the 1x1 layers on the fp16 GEMM; what they do not take (the stride-2 convs) stays on the split GEMM
+        if (m.linear_math == 2 && split3 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
+        if (m.linear_math == 2 && split1 && femasr_gemm_f16_shape_ok(&a)) return CONV_GEMM_F16;
+        if (split3 || split1) return CONV_SPLIT;
     }
     return CONV_DIRECT;
 }
@@ -381,7 +390,8 @@ int gn_tiles(ConvForm f, const femasr_conv_args &a)
 {
     const bool fusable = femasr_gn_fusable(a.Cout);
     switch (f) {
-    case CONV_SPLIT: return 0;
+    case CONV_SPLIT:
+    case CONV_GEMM_F16: return 0;
     case CONV_BF16X3:
     case CONV_F16: return fusable && a.Cout <= 256 ? ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16) : 0;       // <= 8 channels per group
     case CONV_WINO:
@@ -407,18 +417,38 @@ std::array<bool, CONV_FORM_COUNT> layer_forms(const femasr_handle *h, const WSpe
     return can;
 }
 
-// Does the layer run in the fp16 form under decoder_math 4?  Kept out of layer_forms on purpose: a handle that never selects the mode
-// allocates and packs nothing for it (femasr_set_decoder_math builds the images on the first selection, femasr_set_weight keeps them
-// current from then on).
-bool layer_takes_f16(const femasr_handle *h, const WSpec &w)
+// The fp16 weight image the layer needs under the selected fp16 modes: 0 = none, 3 = the 3x3 image (CONV_F16), 1 = the k1 image
+// (CONV_GEMM_F16).  dec: decoder_math 4 (the convs behind every lookup), lin: linear_math 2 (the layers in front of one) - disjoint sets, so a
+// layer's image is built once whichever modes are on.  Kept out of layer_forms on purpose: a handle that never selects such a mode allocates
+// and packs nothing for it (femasr_set_decoder_math / femasr_set_linear_math build the images on the first selection, femasr_set_weight
+// keeps them current from then on).
+int layer_f16_image(const femasr_handle *h, const WSpec &w, bool dec, bool lin)
 {
-    if (w.kind != W_CONV || w.shape[2] != 3) return false;
+    if (w.kind != W_CONV && w.kind != W_LINEAR) return 0;
     femasr_conv_args a{};
     a.B = 1; a.H = 16; a.W = 16; a.Cin = (int)w.shape[1]; a.Cout = (int)w.shape[0];
-    a.ksz = 3; a.stride = 1; a.pad = 1; a.up2 = w.up2;
-    ConvModes m;
-    m.decoder_math = 4;
-    return conv_form(h, m, w.key, a) == CONV_F16;
+    a.ksz = w.kind == W_CONV ? (int)w.shape[2] : 1; a.stride = w.stride; a.pad = a.ksz / 2; a.up2 = w.up2;
+    a.Ho = a.up2 ? 32 : 16 / a.stride; a.Wo = a.Ho;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (!(pass == 0 ? dec : lin)) continue;
+        ConvModes m;
+        m.decoder_math = pass == 0 ? 4 : 0;
+        m.linear_math = pass == 0 ? 1 : 2;
+        const ConvForm f = conv_form(h, m, w.key, a);
+        if (f == CONV_F16) return 3;
+        if (f == CONV_GEMM_F16) return 1;
+    }
+    return 0;
+}
+
+// (re)builds the layer's fp16 image `kind` (layer_f16_image) from the torch-layout tensor, or - oihw == nullptr - from the handle's fp32 image
+// of the same values (the first selection of a mode: the torch tensors are long gone); both give the same bits
+int pack_f16_image(WSpec &w, int kind, const float *oihw)
+{
+    const int O = (int)w.shape[0], I = (int)w.shape[1];
+    if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, kind == 3 ? femasr_packed_weight_f16_bytes(O, I, 3, 3) : femasr_packed_weight_k1_f16_bytes(O, I)));
+    if (kind == 3) return oihw ? femasr_repack_oihw_f16(nullptr, oihw, O, I, 3, 3, w.f16) : femasr_repack_packed_f16(nullptr, w.dev, O, I, w.f16);
+    return oihw ? femasr_repack_k1_f16(nullptr, oihw, O, I, w.f16) : femasr_repack_packed_k1_f16(nullptr, w.dev, O, I, w.f16);
 }
 
 // ---------------------------------------------------------------- forward-time helpers
@@ -498,7 +528,8 @@ struct Ctx {
         const void *image = a.w;
         switch (f) {
         case CONV_BF16X3: image = a.w_bf16x3 = w->bf16x3; break;
-        case CONV_F16: image = a.w_f16 = w->f16; break;
+        case CONV_F16:
+        case CONV_GEMM_F16: image = a.w_f16 = w->f16; break;
         case CONV_WINO:
         case CONV_WINO_UP2: image = a.w_wino = w->wino; a.fast_act = h->modes.decoder_math == 0 ? 1 : 0; break;
         case CONV_SPLIT: image = a.w_bf16s = w->bf16s; break;
@@ -990,10 +1021,8 @@ int femasr_set_weight(femasr_handle *h, const char *key, const float *dev_ptr, c
             if (!w.bf16x3) FEMASR_CHECK_HIP(hipMalloc(&w.bf16x3, femasr_packed_weight_bf16x3_bytes(O, I, 3, 3)));
             rc = femasr_repack_oihw_bf16x3(nullptr, dev_ptr, O, I, 3, 3, w.bf16x3);
         }
-        if (!rc && h->f16_images && layer_takes_f16(h, w)) {       // only once the fp16 mode has been selected
-            if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, femasr_packed_weight_f16_bytes(O, I, 3, 3)));
-            rc = femasr_repack_oihw_f16(nullptr, dev_ptr, O, I, 3, 3, w.f16);
-        }
+        if (!rc)        // only once an fp16 mode that takes the layer has been selected
+            if (const int kind = layer_f16_image(h, w, h->f16_images, h->f16_front_images)) rc = pack_f16_image(w, kind, dev_ptr);
         if (!rc && (can[CONV_WINO] || can[CONV_WINO_UP2])) {
             if (!w.wino) FEMASR_CHECK_HIP(hipMalloc((void **)&w.wino, (w.up2 ? femasr_wino_up2_weight_floats(O, I) : femasr_wino_weight_floats(O, I)) * sizeof(float)));
             rc = w.up2 ? femasr_repack_oihw_wino_up2(nullptr, dev_ptr, O, I, w.wino) : femasr_repack_oihw_wino(nullptr, dev_ptr, O, I, w.wino);
@@ -1241,10 +1270,9 @@ int femasr_set_decoder_math(femasr_handle *h, int mode)
         DeviceGuard guard(h->cfg.device);
         FEMASR_REQUIRE(guard.ok, "set_decoder_math: hipSetDevice(%d) failed", h->cfg.device);
         for (auto &w : h->specs) {
-            if (!w.set || !layer_takes_f16(h, w)) continue;
-            const int O = (int)w.shape[0], I = (int)w.shape[1];
-            if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, femasr_packed_weight_f16_bytes(O, I, 3, 3)));
-            FEMASR_CHECK(femasr_repack_packed_f16(nullptr, w.dev, O, I, w.f16));
+            const int kind = layer_f16_image(h, w, true, false);
+            if (!w.set || !kind || layer_f16_image(h, w, false, h->f16_front_images)) continue;      // (the other fp16 mode already keeps it)
+            FEMASR_CHECK(pack_f16_image(w, kind, nullptr));
         }
         FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
         h->f16_images = true;
@@ -1266,7 +1294,19 @@ int femasr_debug_set_wino_limits(femasr_handle *h, int log2_total, int log2_imag
 
 int femasr_set_linear_math(femasr_handle *h, int mode)
 {
-    FEMASR_REQUIRE(h && (mode == 0 || mode == 1), "set_linear_math: mode must be 0 (fp32 MFMA chain) or 1 (bf16 three-term split)");
+    FEMASR_REQUIRE(h && mode >= 0 && mode <= 2, "set_linear_math: mode must be 0 (fp32 MFMA chain), 1 (bf16 three-term split) or 2 (fp16, one pass)");
+    if (mode == 2 && !h->f16_front_images) {
+        // first selection: the fp16 image of every layer the mode takes, from the handle's fp32 images (as femasr_set_decoder_math does)
+        DeviceGuard guard(h->cfg.device);
+        FEMASR_REQUIRE(guard.ok, "set_linear_math: hipSetDevice(%d) failed", h->cfg.device);
+        for (auto &w : h->specs) {
+            const int kind = layer_f16_image(h, w, false, true);
+            if (!w.set || !kind || layer_f16_image(h, w, h->f16_images, false)) continue;
+            FEMASR_CHECK(pack_f16_image(w, kind, nullptr));
+        }
+        FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
+        h->f16_front_images = true;
+    }
     if (h->modes.linear_math != mode) h->plans.clear();
     h->modes.linear_math = mode;
     return FEMASR_OK;

@@ -28,6 +28,14 @@ def load_weights(model, path):
     return model.load_state_dict(sd, strict=False)
 
 
+class _Half(argparse.Action):
+    """--half: both half-precision modes at once (a later --linear-math / --decoder-math still overrides its side)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.linear_math = 'fp16'
+        namespace.decoder_math = 'fp16'
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description='FeMaSR inference on MI355X')
     ap.add_argument('-i', '--input', type=str, default='inputs', help='Input image or folder')
@@ -42,6 +50,11 @@ def build_parser():
     ap.add_argument('--streams', type=int, default=3, help='sub-batch streams inside one batched forward of the tiled branch (3 measured fastest on MI355X)')
     ap.add_argument('--decoder-math', choices=['fp32', 'fp32_strict', 'fp32_direct', 'bf16x3', 'fp16'], default='fp32',
                     help="arithmetic of the convs behind the codebook lookup (FeMaSRNet.decoder_math); 'fp32_strict' is bit-identical to the CPU oracle; 'fp16' is the fast half-precision mode (same VQ indices, image ~5e-4 of its range off)")
+    ap.add_argument('--linear-math', choices=['bf16_split', 'fp32', 'fp16'], default='bf16_split',
+                    help="arithmetic of the layers in front of the codebook lookup (FeMaSRNet.linear_math); 'fp16' runs the Swin linears and the "
+                         'stride-1 3x3 convs there in one fp16 pass: faster, but VQ indices may differ from the other modes (a nearly tied token can '
+                         'flip and change the image locally by up to ~0.1 of its range)')
+    ap.add_argument('--half', action=_Half, nargs=0, help='shorthand for --linear-math fp16 --decoder-math fp16: the whole network half-precision grade')
     ap.add_argument('--blend', action='store_true',
                     help='tiled branch: blend the overlapping tile halos instead of discarding them (no seams between tiles; NOT the '
                          "reference's arithmetic, off by default; needs 2 * tile_pad <= tile_size)")
@@ -75,6 +88,7 @@ def main(argv=None):
     else:
         raise SystemExit('no network here: pass -w <weights.pth> (FeMaSR_SRX4/SRX2_model_g.pth) or --synthetic-seed N')
     model.decoder_math = args.decoder_math
+    model.linear_math = args.linear_math
     if not 1 <= args.color_fix_levels <= 12:
         raise SystemExit(f'--color-fix-levels must be in 1..12, got {args.color_fix_levels}')
     model.color_fix_levels = args.color_fix_levels

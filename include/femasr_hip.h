@@ -59,7 +59,8 @@ typedef struct {
 } femasr_config;
 
 const char *femasr_last_error(void);
-/* 100 * major + minor.  107: femasr_conv_args ends with w_f16; femasr_repack_oihw_f16 / femasr_packed_weight_f16_bytes; femasr_set_decoder_math takes 4 ('fp16').  106: femasr_blend_tiles / femasr_blend_tiles_u8 (the opt-in overlap-blend paste).  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
+/* 100 * major + minor.  107 (additive since: femasr_repack_k1_f16 / femasr_packed_weight_k1_f16_bytes, the ksz = 1 meaning of w_f16 and
+ * femasr_set_linear_math mode 2; the struct layout and every earlier entry point are unchanged, so the number stays): femasr_conv_args ends with w_f16; femasr_repack_oihw_f16 / femasr_packed_weight_f16_bytes; femasr_set_decoder_math takes 4 ('fp16').  106: femasr_blend_tiles / femasr_blend_tiles_u8 (the opt-in overlap-blend paste).  105: the femasr_niqe_* and femasr_imresize* entry points.  104: the femasr_psnr_ssim* entry points and femasr_ssim_window.  103: FEMASR_ACT_RELU and the femasr_lpips_* entry points (femasr_conv_args is unchanged).  102: the debug hooks moved to femasr_hip_debug.h; femasr_mlp_fused and the process-global femasr_debug_wino_* switches are gone;
  * femasr_extract_tiles_u8 / femasr_paste_tiles_u8 are new (femasr_conv_args is unchanged since 101). */
 int femasr_version(void);
 
@@ -217,7 +218,17 @@ typedef struct {
                              Every output element is within 128 * 2^-24 * sum_k |t16_k w16_k| of conv(t16, w16) evaluated exactly, plus
                              the fp32 roundings of bias / residuals and, with the prologue, one fp16 ulp of t_k times |w16_k| wherever the
                              SiLU's 8 fp32 ulp straddle an fp16 rounding boundary (tests/test_gpu_decoder_fp16.py).  gn_part as for
-                             w_bf16x3 (Cout / 32 a power of two <= 8).  `w` is not read. */
+                             w_bf16x3 (Cout / 32 a power of two <= 8).  `w` is not read.
+                             With ksz = 1 (the k1 meaning; weights from femasr_repack_k1_f16): a 1x1 stride-1 layer / nn.Linear under the k1 shape
+                             rule of w_bf16s (Cin % 64 == 0, pad 0, no prologue, no up2) runs as ONE fp16 GEMM pass (kernels_gemm_f16.hip):
+                               a16 = fp16_rne(clamp(a, +-65504)) of the fp32 input row, w16 = fp16_rne(w) (subnormals with their value)
+                               out = epi(bias + sum_k a16_k * w16_k): products exact, accumulated in fp32 by v_mfma_f32_32x32x16_f16 with k
+                                     ascending; bias (may be NULL = 0) in fp32; act = GELU by the split GEMM's device function; ONE residual
+                                     (res1 or res2) added in fp32; stored as fp32.
+                             Three epilogues exist - plain, GELU, one residual -; GELU with a residual, or two residuals, is refused.  Every
+                             output element is within 128 * 2^-24 * sum_k |a16_k w16_k| + 2 * 2^-24 (|bias| + |res| + |ref|) of the exact value
+                             (tests/test_gpu_linear_fp16.py).  FeMaSRNet's linear_math 'fp16' uses both meanings for the layers in FRONT of the
+                             codebook lookup: VQ indices may then differ from the other modes (femasr_set_linear_math). */
 } femasr_conv_args;
 /* Size limits (each a shape rule evaluated before any launch; DESIGN.md 5.7, tests/test_gpu_product_anchor.py):
  *   rows B*Ho*Wo < 2^31 - 256 for every form, else FEMASR_ERR_INVALID;
@@ -357,9 +368,23 @@ int femasr_repack_k1_bf16s(void *stream, const float *w_oi, int O, int I, void *
  * fema_utils.py:65-84) and the conv behind every RSTB (network_swinir.py:465). */
 size_t femasr_packed_weight_conv3x3_bf16s_bytes(int O, int I);
 int femasr_repack_oihw_bf16s(void *stream, const float *w_oihw, int O, int I, void *out);
-/* Arithmetic of the network's 1x1 convs / nn.Linear layers (the Swin qkv / proj / fc1 / fc2 and before_quant):
+/* (out, in) fp32 -> femasr_conv_args.w_f16 of a 1x1 layer (ksz = 1): fp16 (round to nearest even), packed [Cin/16][ceil(Cout/32)][lane][8 halves] -
+ * the MFMA B fragments of one 16-channel step, 1 KiB per column tile, zero padded in Cout.  Cin % 64 == 0 (bytes: 0 otherwise). */
+size_t femasr_packed_weight_k1_f16_bytes(int O, int I);
+int femasr_repack_k1_f16(void *stream, const float *w_oi, int O, int I, void *out);
+/* Arithmetic of the network's 1x1 convs / nn.Linear layers (the Swin qkv / proj / fc1 / fc2 and before_quant) and of the 3x3 convs in front of
+ * the codebook lookup:
  * 1 (default, 'bf16_split'): the fp32-grade product on the bf16 matrix pipe described at femasr_conv_args.w_bf16s;
- * 0 ('fp32'): one fp32 fmaf chain per output on the fp32 MFMA (kernels_gemm.hip), bit-identical to OracleNet(linear_math='fp32'). */
+ * 0 ('fp32'): one fp32 fmaf chain per output on the fp32 MFMA (kernels_gemm.hip), bit-identical to OracleNet(linear_math='fp32');
+ * 2 ('fp16', opt-in): HALF-precision grade in front of the lookup.  Exactly the layers mode 1 sends to the split GEMM are taken: the 1x1
+ *    stride-1 layers run as the one-pass fp16 GEMM (w_f16 with ksz = 1), the 3x3 stride-1 pad-1 convs that pass the w_f16 shape rule run in the
+ *    one-pass fp16 halo form with its fused GroupNorm + SiLU prologue (hardware exp2 / rcp units) and fused GroupNorm partials - the
+ *    stand-alone femasr_gn_silu_apply pass in front of them and the moments pass behind them disappear.  Everything else (stride-2 convs,
+ *    in_conv, attention, LayerNorm, the lookup) runs as in mode 1.  Results are deterministic and bitwise independent of batch size, streams,
+ *    graph replay and tiling within the mode, but VQ indices are NOT guaranteed equal to the other modes' and the image is NOT within their
+ *    1e-3 bound: a token whose two nearest codes are nearly tied may flip, and the image changes locally by up to ~0.1 of unit range there
+ *    (DESIGN.md 17 has the measured rates).  Orthogonal to femasr_set_decoder_math.  The fp16 weight images are built when the mode is first
+ *    selected and kept current by femasr_set_weight from then on; a handle that never selects it allocates nothing for it. */
 int femasr_set_linear_math(femasr_handle *h, int mode);
 
 /* Split-bf16 (hi/lo) fragment-major weights for the opt-in bf16x3 conv path (3x3 convs behind the VQ lookup). */
