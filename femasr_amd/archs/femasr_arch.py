@@ -253,13 +253,13 @@ class FeMaSRNet(nn.Module):
         self.color_fix_levels = 5
         self.debug_wino_limits = None   # tests only: (log2_total, log2_image) for this net's planner (include/femasr_hip_debug.h)
 
-    DECODER_MATH = {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3, 'fp16': 4}      # femasr_set_decoder_math
+    DECODER_MATH = {'fp32': 0, 'bf16x3': 1, 'fp32_direct': 2, 'fp32_strict': 3, 'fp16': 4}      # femasr_set_decoder_math: the FEMASR_DECODER_MATH_* values of include/femasr_hip.h
 
     def _check_decoder_math(self):
         if self.decoder_math not in self.DECODER_MATH:
             raise ValueError(f"decoder_math must be 'fp32', 'fp32_strict', 'fp32_direct', 'bf16x3' or 'fp16', got {self.decoder_math!r}")
 
-    LINEAR_MATH = {'fp32': 0, 'bf16_split': 1, 'fp16': 2}      # femasr_set_linear_math
+    LINEAR_MATH = {'fp32': 0, 'bf16_split': 1, 'fp16': 2}      # femasr_set_linear_math: the FEMASR_LINEAR_MATH_* values of include/femasr_hip.h
 
     def _check_linear_math(self):
         if self.linear_math not in self.LINEAR_MATH:

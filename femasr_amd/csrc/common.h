@@ -68,53 +68,43 @@ int femasr_gemm_pick_variant(const femasr_conv_args *a, bool vq);
 const char *femasr_gemm_variant_name(int v);
 int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out);
 
-// 1x1 convs / nn.Linear as an fp32-grade product on the bf16 matrix pipe (kernels_gemm_bf16.hip)
-bool femasr_gemm_bf16s_shape_ok(const femasr_conv_args *a);
+// What the translation unit of a conv form defines under its prefix besides the launch: the pointer-free shape rule, the variant table
+// (names in profile-slot order) and the variant a call runs (shape-only)
+#define FEMASR_FORM_DECLS(prefix)                                          \
+    bool femasr_##prefix##_shape_ok(const femasr_conv_args *a);            \
+    int femasr_##prefix##_variant_count();                                 \
+    const char *femasr_##prefix##_variant_name(int v);                     \
+    int femasr_##prefix##_pick_variant(const femasr_conv_args *a)
+
+// 1x1 convs / nn.Linear as an fp32-grade product on the bf16 matrix pipe (kernels_gemm_bf16.hip); shape_ok: a 1x1 layer or the 3x3 form
+FEMASR_FORM_DECLS(gemm_bf16s);
 bool femasr_conv3x3_bf16s_shape_ok(const femasr_conv_args *a);      // the 3x3 pad-1 form (K = 9 Cin, stride 1 or 2) of the same kernel
 int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const void *w_bf16s, int *variant_out, double *flops_out);
-int femasr_gemm_bf16s_variant_count();
-int femasr_gemm_bf16s_pick_variant(const femasr_conv_args *a);
-const char *femasr_gemm_bf16s_variant_name(int v);
 
 // Winograd F(4x4,3x3) 3x3 convs (kernels_wino.hip)
 constexpr int FEMASR_WINO_LOG2_TOTAL = 31, FEMASR_WINO_LOG2_IMAGE = 27;      // element limits of the Winograd-form kernels (32-bit byte offsets)
-bool femasr_conv_wino_shape_ok(const femasr_conv_args *a);
+FEMASR_FORM_DECLS(conv_wino);
+int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
 bool femasr_conv_wino_shape_ok_lim(const femasr_conv_args *a, int log2_total, int log2_image);      // a handle's planner may lower the limits (femasr_debug_set_wino_limits)
 int femasr_conv_wino_gn_tiles(int H, int W);      // fused GroupNorm partials of a Winograd conv: one per 16x16-pixel sub-block
-int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
-int femasr_conv_wino_variant_count();
-int femasr_conv_wino_pick_variant(const femasr_conv_args *a);
-const char *femasr_conv_wino_variant_name(int v);
-// nn.Upsample(x2) + 3x3 conv in the 25-product Winograd-type form (kernels_wino_up2.hip); GroupNorm partials per 16x16 OUTPUT sub-block
+// nn.Upsample(x2) + 3x3 conv in the 25-product Winograd-type form (kernels_wino_up2.hip), one variant; GroupNorm partials per 16x16 OUTPUT sub-block
 bool femasr_conv_wino_up2_shape_ok(const femasr_conv_args *a);
 bool femasr_conv_wino_up2_shape_ok_lim(const femasr_conv_args *a, int log2_total, int log2_image);
 int femasr_conv_wino_up2_launch(hipStream_t s, const femasr_conv_args *a, double *flops_out);
 const char *femasr_conv_wino_up2_variant_name();
 
 // bf16x3 3x3 halo convs (kernels_conv_bf16.hip)
-bool femasr_conv_bf16x3_eligible(const femasr_conv_args *a);
-bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a);      // the same rule without the w_bf16x3 pointer (planner)
+FEMASR_FORM_DECLS(conv_bf16x3);
 int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
-int femasr_conv_bf16x3_variant_count();
-int femasr_conv_bf16x3_pick_variant(const femasr_conv_args *a);
-const char *femasr_conv_bf16x3_variant_name(int v);
-
-// one-pass fp16 3x3 halo convs (kernels_conv_f16.hip): the bf16x3 form's layers and shape rule, decoder_math 4
-bool femasr_conv_f16_eligible(const femasr_conv_args *a);
-bool femasr_conv_f16_shape_ok(const femasr_conv_args *a);         // the same rule without the w_f16 pointer (planner)
+// one-pass fp16 3x3 halo convs (kernels_conv_f16.hip): the bf16x3 form's layers and shape rule, FEMASR_DECODER_MATH_FP16
+FEMASR_FORM_DECLS(conv_f16);
 int femasr_conv_f16_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
-int femasr_conv_f16_variant_count();
-int femasr_conv_f16_pick_variant(const femasr_conv_args *a);
-const char *femasr_conv_f16_variant_name(int v);
 // the fp16 image built from the layer's fragment-major fp32 image (femasr_repack_oihw of a 3x3 conv with I % 32 == 0) instead of the OIHW tensor
 int femasr_repack_packed_f16(hipStream_t stream, const float *packed, int O, int I, void *out);
 
-// one-pass fp16 GEMM of the 1x1 layers (kernels_gemm_f16.hip): the split GEMM's k1 layers and shape rule, linear_math 2
-bool femasr_gemm_f16_shape_ok(const femasr_conv_args *a);
+// one-pass fp16 GEMM of the 1x1 layers (kernels_gemm_f16.hip): the split GEMM's k1 layers and shape rule, FEMASR_LINEAR_MATH_FP16
+FEMASR_FORM_DECLS(gemm_f16);
 int femasr_gemm_f16_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
-int femasr_gemm_f16_variant_count();
-int femasr_gemm_f16_pick_variant(const femasr_conv_args *a);
-const char *femasr_gemm_f16_variant_name(int v);
 // the fp16 image built from the layer's GEMM-layout fp32 image (femasr_repack_oihw with kh = kw = 1) instead of the (out, in) tensor
 int femasr_repack_packed_k1_f16(hipStream_t stream, const float *packed, int O, int I, void *out);
 
@@ -129,8 +119,40 @@ enum ConvForm {
     CONV_GEMM_F16,    // one-pass fp16 GEMM of a 1x1 layer (w_f16 with ksz = 1); new forms go last, so the slots of the others keep their numbers
     CONV_FORM_COUNT
 };
-int femasr_conv_form_variant_count(ConvForm f);
-const char *femasr_conv_form_variant_name(ConvForm f, int v);
-// Launches the conv in form f (the form's weight image in its femasr_conv_args field; w_bf16s for CONV_SPLIT).  *slot_out: the
-// launch's profile slot counted from the first conv slot (variants of the forms before f, then the variant that ran).
+
+// Everything the library knows about a form, one row each in kConvForms (kernels_misc.hip): a new form is an enum value, a row, its kernel
+// file and its place in conv_form()'s precedence (model.hip).
+struct ConvFormDesc {
+    ConvForm form;      // the row's own index (femasr_create asserts it)
+    // the kernels: variants in profile-slot order, the variant a call runs (shape-only), the launch
+    int (*variant_count)();
+    const char *(*variant_name)(int v);
+    int (*pick_variant)(const femasr_conv_args *a);
+    int (*launch)(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out);
+    // the weight image: the femasr_conv_args field that carries it (offsetof), its size and its repack from the torch-layout tensor
+    // (OIHW with ksz x ksz taps, (out, in) with ksz = 1); from_packed, where the form has one, builds it from the layer's CONV_DIRECT image
+    size_t field;
+    size_t (*image_bytes)(int O, int I, int ksz);
+    int (*repack)(const float *w, int O, int I, int ksz, void *out);
+    int (*from_packed)(hipStream_t s, const float *packed, int O, int I, void *out);
+    // femasr_conv2d runs the form of lowest `rank` whose image is given and whose `chosen` (null = always) holds, and refuses with
+    // `refusal` unless the pointer-free shape rule (null = the launch checks) accepts the call
+    int rank;
+    bool (*chosen)(const femasr_conv_args *a);
+    bool (*shape_ok)(const femasr_conv_args *a);
+    const char *refusal;
+    // fused GroupNorm partial moments a conv of this form writes when its output feeds a GroupNorm: tiles per sample (null = none: the
+    // GroupNorm then runs the stand-alone moments kernel, which gives the same coefficients bit for bit)
+    int (*gn_tiles)(const femasr_conv_args *a);
+};
+const ConvFormDesc &femasr_conv_form_desc(int f);      // row f of kConvForms, f a ConvForm
+inline const void *femasr_conv_form_image(int f, const femasr_conv_args *a)
+{
+    const void *p;
+    __builtin_memcpy(&p, (const char *)a + femasr_conv_form_desc(f).field, sizeof p);
+    return p;
+}
+inline void femasr_conv_form_set_image(int f, femasr_conv_args *a, const void *image) { __builtin_memcpy((char *)a + femasr_conv_form_desc(f).field, &image, sizeof image); }
+// Launches the conv in form f (the form's weight image in its femasr_conv_args field).  *slot_out: the launch's profile slot counted
+// from the first conv slot (variants of the forms before f, then the variant that ran).
 int femasr_conv_form_launch(hipStream_t s, ConvForm f, const femasr_conv_args *a, int *slot_out, double *flops_out);

@@ -77,5 +77,45 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk)
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
 }
 
+// Host side of the two matrix-core halo forms (kernels_conv_bf16.hip, kernels_conv_f16.hip): a row of a form's variant table and the
+// launch of the row `pick` names.  who: the first word of the messages; image: the form's weight fragments (the field of *a, or null).
+struct HaloVariant {
+    const char *name;
+    int bn, threads;
+    void (*kern)(const ConvParams, const uint4 *, double *);
+    size_t lds;
+    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d (the attribute is per device)
+};
+
+template <int N>
+int halo_variant_launch(hipStream_t s, const femasr_conv_args *a, const char *who, HaloVariant (&table)[N], const void *image,
+                        bool (*shape_ok)(const femasr_conv_args *), int (*pick)(const femasr_conv_args *), int *variant_out, double *flops_out)
+{
+    FEMASR_REQUIRE(a && a->in && a->bias && a->out && image && shape_ok(a), "%s: not eligible", who);
+    const int Hv = a->up2 ? 2 * a->H : a->H, Wv = a->up2 ? 2 * a->W : a->W;
+    FEMASR_REQUIRE(Hv == a->Ho && Wv == a->Wo, "%s: Ho/Wo mismatch", who);
+    if (a->prologue == FEMASR_PRO_GN_SILU) FEMASR_REQUIRE(a->pro_a && a->pro_b, "%s: GN prologue needs a,b", who);
+    ConvParams p{};
+    p.in = a->in; p.bias = a->bias; p.pro_a = a->pro_a; p.pro_b = a->pro_b; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
+    p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.ksz = 3; p.stride = 1; p.pad = 1; p.up2 = a->up2;
+    p.Ho = Hv; p.Wo = Wv; p.NT32 = (a->Cout + 31) / 32;
+    const int vi = pick(a);
+    HaloVariant &v = table[vi];
+    p.tilesX = (p.Wo + 15) / 16;
+    p.tilesY = (p.Ho + 7) / 8;
+    p.MB = a->B * p.tilesX * p.tilesY;
+    p.NB = (a->Cout + v.bn - 1) / v.bn;
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds + 40 * 1024));
+    size_t lds = v.lds + (a->prologue == FEMASR_PRO_GN_SILU ? (size_t)2 * a->Cin * sizeof(float) : 0);
+    const size_t epi = 8192 + (size_t)(v.threads / 64) * 32 * 36 * sizeof(float);       // epilogue transpose scratch
+    if (lds < epi) lds = epi;
+    FEMASR_REQUIRE(!a->gn_part || (a->Cout % 32 == 0 && (a->Cout / 32) <= 8 && ((a->Cout / 32) & (a->Cout / 32 - 1)) == 0),
+                   "%s: fused GN moments need Cout = 32 * {1, 2, 4, 8} (32 groups, power-of-two channels per group)", who);
+    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3((unsigned)v.threads), lds, s, p, (const uint4 *)image, (double *)a->gn_part);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    if (variant_out) *variant_out = vi;
+    if (flops_out) *flops_out = 2.0 * (double)a->B * p.Ho * p.Wo * (double)a->Cout * 9.0 * a->Cin;
+    return FEMASR_OK;
+}
 
 }  // namespace

@@ -519,18 +519,11 @@ __global__ void repack_oihw_bf16x3_kernel(const float *__restrict__ in, int O, i
 template <int BN, bool UP2>
 constexpr size_t bf16_lds_bytes() { return (size_t)((BN <= 64 && !UP2) ? 1 : 2) * 2 * ((UP2 ? 60 : 180) + 1) * PPITCH * sizeof(unsigned short); }   // + 2*Cin floats (GN)
 
-struct Variant16 {
-    const char *name;
-    int bn, threads;
-    void (*kern)(const ConvParams, const uint4 *, double *);
-    size_t lds;
-    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d (the attribute is per device)
-};
 #define FEMASR_H16(BN, WM, WN, PRO, UP2)                                                        \
     { "conv3x3_halo_bf16x3<8x16x" #BN "," #PRO ",up2=" #UP2 ",waves=" #WM "x" #WN ">", BN, WM * WN * 64,   \
       conv3x3_halo_bf16x3_kernel<BN, WM, WN, PRO, UP2>, bf16_lds_bytes<BN, UP2>(), 0ull }
 
-Variant16 g_v16[] = {
+HaloVariant g_v16[] = {
     FEMASR_H16(128, 2, 2, FEMASR_PRO_NONE, false),     // 0   (4 waves: 64 px x 64 ch per wave)
     FEMASR_H16(128, 2, 2, FEMASR_PRO_GN_SILU, false),  // 1
     FEMASR_H16(128, 2, 2, FEMASR_PRO_NONE, true),      // 2
@@ -557,8 +550,6 @@ constexpr int kNum16 = sizeof(g_v16) / sizeof(g_v16[0]);
 int femasr_conv_bf16x3_variant_count() { return kNum16; }
 const char *femasr_conv_bf16x3_variant_name(int v) { return (v >= 0 && v < kNum16) ? g_v16[v].name : "?"; }
 
-bool femasr_conv_bf16x3_eligible(const femasr_conv_args *a) { return a->w_bf16x3 && femasr_conv_bf16x3_shape_ok(a); }
-
 bool femasr_conv_bf16x3_shape_ok(const femasr_conv_args *a)
 {
     return a->ksz == 3 && a->stride == 1 && a->pad == 1 && (a->Cin % BK) == 0 &&
@@ -576,34 +567,9 @@ int femasr_conv_bf16x3_pick_variant(const femasr_conv_args *a)
 
 int femasr_conv_bf16x3_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out)
 {
-    FEMASR_REQUIRE(a && a->in && a->bias && a->out && femasr_conv_bf16x3_eligible(a), "conv bf16x3: not eligible");
-    const int Hv = a->up2 ? 2 * a->H : a->H, Wv = a->up2 ? 2 * a->W : a->W;
-    FEMASR_REQUIRE(Hv == a->Ho && Wv == a->Wo, "conv bf16x3: Ho/Wo mismatch");
-    if (a->prologue == FEMASR_PRO_GN_SILU) FEMASR_REQUIRE(a->pro_a && a->pro_b, "conv bf16x3: GN prologue needs a,b");
-    ConvParams p{};
-    p.in = a->in; p.bias = a->bias; p.pro_a = a->pro_a; p.pro_b = a->pro_b; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.ksz = 3; p.stride = 1; p.pad = 1; p.up2 = a->up2;
-    p.Ho = Hv; p.Wo = Wv; p.NT32 = (a->Cout + 31) / 32;
-    const int vi = femasr_conv_bf16x3_pick_variant(a);
-    Variant16 &v = g_v16[vi];
-    p.tilesX = (p.Wo + 15) / 16;
-    p.tilesY = (p.Ho + 7) / 8;
-    p.MB = a->B * p.tilesX * p.tilesY;
-    p.NB = (a->Cout + v.bn - 1) / v.bn;
-    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds + 40 * 1024));
-    size_t lds = v.lds + (a->prologue == FEMASR_PRO_GN_SILU ? (size_t)2 * a->Cin * sizeof(float) : 0);
-    const size_t epi = 8192 + (size_t)(v.threads / 64) * 32 * 36 * sizeof(float);       // epilogue transpose scratch
-    if (lds < epi) lds = epi;
-    FEMASR_REQUIRE(!a->gn_part || (a->Cout % 32 == 0 && (a->Cout / 32) <= 8 && ((a->Cout / 32) & (a->Cout / 32 - 1)) == 0),
-                   "conv bf16x3: fused GN moments need Cout = 32 * {1, 2, 4, 8} (32 groups, power-of-two channels per group)");
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3((unsigned)v.threads), lds, s, p, (const uint4 *)a->w_bf16x3,
-                       (double *)a->gn_part);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    if (variant_out) *variant_out = vi;
-    if (flops_out) *flops_out = 2.0 * (double)a->B * p.Ho * p.Wo * (double)a->Cout * 9.0 * a->Cin;
-    return FEMASR_OK;
+    return halo_variant_launch(s, a, "conv bf16x3", g_v16, a ? a->w_bf16x3 : nullptr, femasr_conv_bf16x3_shape_ok, femasr_conv_bf16x3_pick_variant,
+                               variant_out, flops_out);
 }
-
 
 extern "C" {
 

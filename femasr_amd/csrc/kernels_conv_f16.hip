@@ -409,18 +409,11 @@ __global__ void repack_f16_kernel(const float *__restrict__ in, int O, int I, in
 template <bool UP2>
 constexpr size_t f16_lds_bytes() { return (size_t)2 * ((UP2 ? 60 : 180) + 1) * PPITCH * sizeof(unsigned short); }   // + 2*Cin floats (GN)
 
-struct VariantF16 {
-    const char *name;
-    int bn, threads;
-    void (*kern)(const ConvParams, const uint4 *, double *);
-    size_t lds;
-    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d (the attribute is per device)
-};
 #define FEMASR_HF16(BN, WM, WN, PRO, UP2)                                                        \
     { "conv3x3_halo_f16<8x16x" #BN "," #PRO ",up2=" #UP2 ",waves=" #WM "x" #WN ">", BN, WM * WN * 64,   \
       conv3x3_halo_f16_kernel<BN, WM, WN, PRO, UP2>, f16_lds_bytes<UP2>(), 0ull }
 
-VariantF16 g_vf16[] = {
+HaloVariant g_vf16[] = {
     FEMASR_HF16(128, 2, 2, FEMASR_PRO_NONE, false),     // 0   Cout 65..128: 64 px x 64 ch per wave
     FEMASR_HF16(128, 2, 2, FEMASR_PRO_GN_SILU, false),  // 1
     FEMASR_HF16(128, 2, 2, FEMASR_PRO_NONE, true),      // 2
@@ -443,7 +436,6 @@ const char *femasr_conv_f16_variant_name(int v) { return (v >= 0 && v < kNumF16)
 
 // the shape and size rule of the bf16x3 form: the two forms take the same layers
 bool femasr_conv_f16_shape_ok(const femasr_conv_args *a) { return femasr_conv_bf16x3_shape_ok(a); }
-bool femasr_conv_f16_eligible(const femasr_conv_args *a) { return a->w_f16 && femasr_conv_f16_shape_ok(a); }
 
 int femasr_conv_f16_pick_variant(const femasr_conv_args *a)
 {
@@ -453,32 +445,7 @@ int femasr_conv_f16_pick_variant(const femasr_conv_args *a)
 
 int femasr_conv_f16_launch(hipStream_t s, const femasr_conv_args *a, int *variant_out, double *flops_out)
 {
-    FEMASR_REQUIRE(a && a->in && a->bias && a->out && femasr_conv_f16_eligible(a), "conv f16: not eligible");
-    const int Hv = a->up2 ? 2 * a->H : a->H, Wv = a->up2 ? 2 * a->W : a->W;
-    FEMASR_REQUIRE(Hv == a->Ho && Wv == a->Wo, "conv f16: Ho/Wo mismatch");
-    if (a->prologue == FEMASR_PRO_GN_SILU) FEMASR_REQUIRE(a->pro_a && a->pro_b, "conv f16: GN prologue needs a,b");
-    ConvParams p{};
-    p.in = a->in; p.bias = a->bias; p.pro_a = a->pro_a; p.pro_b = a->pro_b; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.ksz = 3; p.stride = 1; p.pad = 1; p.up2 = a->up2;
-    p.Ho = Hv; p.Wo = Wv; p.NT32 = (a->Cout + 31) / 32;
-    const int vi = femasr_conv_f16_pick_variant(a);
-    VariantF16 &v = g_vf16[vi];
-    p.tilesX = (p.Wo + 15) / 16;
-    p.tilesY = (p.Ho + 7) / 8;
-    p.MB = a->B * p.tilesX * p.tilesY;
-    p.NB = (a->Cout + v.bn - 1) / v.bn;
-    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds + 40 * 1024));
-    size_t lds = v.lds + (a->prologue == FEMASR_PRO_GN_SILU ? (size_t)2 * a->Cin * sizeof(float) : 0);
-    const size_t epi = 8192 + (size_t)(v.threads / 64) * 32 * 36 * sizeof(float);       // epilogue transpose scratch
-    if (lds < epi) lds = epi;
-    FEMASR_REQUIRE(!a->gn_part || (a->Cout % 32 == 0 && (a->Cout / 32) <= 8 && ((a->Cout / 32) & (a->Cout / 32 - 1)) == 0),
-                   "conv f16: fused GN moments need Cout = 32 * {1, 2, 4, 8} (32 groups, power-of-two channels per group)");
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3((unsigned)v.threads), lds, s, p, (const uint4 *)a->w_f16,
-                       (double *)a->gn_part);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    if (variant_out) *variant_out = vi;
-    if (flops_out) *flops_out = 2.0 * (double)a->B * p.Ho * p.Wo * (double)a->Cout * 9.0 * a->Cin;
-    return FEMASR_OK;
+    return halo_variant_launch(s, a, "conv f16", g_vf16, a ? a->w_f16 : nullptr, femasr_conv_f16_shape_ok, femasr_conv_f16_pick_variant, variant_out, flops_out);
 }
 
 // the fp16 image of a layer from its fragment-major fp32 image (femasr_repack_oihw; 3x3, I % 32 == 0): model.hip, first selection of mode 4

@@ -11,6 +11,7 @@
 // but on NHWC activations, with every elementwise / normalisation op folded into the
 // neighbouring implicit-GEMM launch (see kernels_conv.hip) — about 300 launches per forward,
 // all on the caller's stream, no host synchronisation.
+#include <assert.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -78,14 +79,12 @@ struct WSpec {
     WKind kind;
     int64_t shape[4];
     int ndim;
-    // owned weight images; femasr_set_weight builds those of every form the layer can take (layer_forms)
-    float *dev = nullptr;   // repacked fp32 (CONV_DIRECT)
+    // owned weight images by form (kConvForms): a conv / linear layer holds those of every form it can take (layer_forms) - at most one
+    // of the two Winograd forms and one of the two fp16 forms; any other weight is the tensor itself, in image[CONV_DIRECT]
+    void *image[CONV_FORM_COUNT] = {};
     float *up2w = nullptr;  // phase matrices of a nearest-x2 conv (femasr_repack_oihw_up2; CONV_DIRECT on the halo kernels)
-    void *bf16x3 = nullptr; // bf16x3 hi/lo fragments (CONV_BF16X3)
-    float *wino = nullptr;  // Winograd-domain weights (CONV_WINO / CONV_WINO_UP2)
-    void *f16 = nullptr;    // fp16 fragments (CONV_F16 of a 3x3 conv, CONV_GEMM_F16 of a 1x1 layer): built only once the handle has selected a mode
-                            // that runs the layer in that form (decoder_math 4 / linear_math 2; layer_f16_image)
-    void *bf16s = nullptr;  // three bf16 planes of the (K x Cout) matrix (CONV_SPLIT: femasr_repack_k1_bf16s / femasr_repack_oihw_bf16s)
+    float *dev() const { return (float *)image[CONV_DIRECT]; }
+    int ksz() const { return kind == W_CONV ? (int)shape[2] : 1; }      // (square kernels)
     bool up2 = false;       // the conv behind nn.Upsample(x2) of an up / decoder block
     int stride = 1;         // 2: a down conv of the encoder
     bool set = false;
@@ -169,8 +168,8 @@ struct Arena {
 struct ProfRec { int slot; hipEvent_t e0, e1; double flops, bytes; };
 
 struct ConvModes {          // the handle's settings that choose the form of a conv (conv_form)
-    int decoder_math = 0;   // femasr_set_decoder_math
-    int linear_math = 1;    // femasr_set_linear_math: 1 = fp32-grade product on the bf16 matrix pipe, 0 = fp32 MFMA chain, 2 = one fp16 pass
+    int decoder_math = FEMASR_DECODER_MATH_FP32;        // femasr_set_decoder_math
+    int linear_math = FEMASR_LINEAR_MATH_BF16_SPLIT;    // femasr_set_linear_math
     int wino_log2_total = FEMASR_WINO_LOG2_TOTAL, wino_log2_image = FEMASR_WINO_LOG2_IMAGE;      // femasr_debug_set_wino_limits (planner only)
 };
 
@@ -185,8 +184,10 @@ struct femasr_handle {
     float *cbT[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr}, *ee[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr};
     void *vq_aux[FEMASR_MAX_CODEBOOKS] = {nullptr, nullptr, nullptr};       // bf16 codebook image of the two-pass search
     bool finalized = false;
-    bool f16_images = false;        // decoder_math 4 has been selected once: the CONV_F16 layers keep an fp16 weight image from then on
-    bool f16_front_images = false;  // linear_math 2 has been selected once: the same for the layers that mode takes (in front of the lookup)
+    // the mode values ever selected, one bit each: the layers keep a weight image for every form these modes can give them (layer_forms).
+    // From creation every mode but the two fp16 ones; those join when first selected, so a handle that never selects one packs nothing for it
+    unsigned decoder_seen = ((1u << FEMASR_DECODER_MATH_COUNT) - 1) & ~(1u << FEMASR_DECODER_MATH_FP16);
+    unsigned linear_seen = ((1u << FEMASR_LINEAR_MATH_COUNT) - 1) & ~(1u << FEMASR_LINEAR_MATH_FP16);
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -355,18 +356,18 @@ int build_specs(femasr_handle *h)
 ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string &key, const femasr_conv_args &a)
 {
     const bool behind = behind_every_lookup(h->cfg, h->encode_depth, h->last_quant_stage, key);
-    if (behind && m.decoder_math == 1 && a.Cout > 4 && femasr_conv_bf16x3_shape_ok(&a)) return CONV_BF16X3;   // out_conv: exact VALU kernel in every mode
+    if (behind && m.decoder_math == FEMASR_DECODER_MATH_BF16X3 && a.Cout > 4 && femasr_conv_bf16x3_shape_ok(&a)) return CONV_BF16X3;   // out_conv: exact VALU kernel in every mode
     // decoder_math 4 = 'fp16': the same layers, by the same rule, in the one-pass fp16 form; a layer outside the rule falls through to
     // what it takes in 'fp32_direct'
-    if (behind && m.decoder_math == 4 && a.Cout > 4 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
+    if (behind && m.decoder_math == FEMASR_DECODER_MATH_FP16 && a.Cout > 4 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
     // exact-fp32 mode: convs behind every codebook lookup run in the Winograd F(4x4,3x3) form, the x2 convs in the 25-product form
     // (they cannot move a VQ index; oracle: OracleNet.wino).  decoder_math 2 = 'fp32_direct' keeps the direct form; 0 runs the
     // SiLU of their GroupNorm prologue on the hardware exp2 / rcp units, 3 = 'fp32_strict' keeps it IEEE-exact (== oracle).
-    if (behind && (m.decoder_math == 0 || m.decoder_math == 3)) {
+    if (behind && (m.decoder_math == FEMASR_DECODER_MATH_FP32 || m.decoder_math == FEMASR_DECODER_MATH_FP32_STRICT)) {
         if (femasr_conv_wino_up2_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO_UP2;
         if (femasr_conv_wino_shape_ok_lim(&a, m.wino_log2_total, m.wino_log2_image)) return CONV_WINO;
     }
-    if (m.linear_math >= 1) {
+    if (m.linear_math != FEMASR_LINEAR_MATH_FP32) {
         // a 3x3 conv in FRONT of a lookup (encoder down convs and ResBlocks, the conv behind every RSTB) runs as the split-bf16 GEMM
         // over K = 9 Cin - the arithmetic of the linear layers (oracle: conv3x3_bf16s).  Its GroupNorm + SiLU prologue becomes a pass
         // of its own (the GEMM takes plain rows).
@@ -377,78 +378,55 @@ ConvForm conv_form(const femasr_handle *h, const ConvModes &m, const std::string
         // linear_math 2 = 'fp16': exactly these layers, in ONE fp16 pass where the fp16 kernels' own shape rules hold - the stride-1 3x3 convs in
         // the fp16 halo form (its fused GroupNorm + SiLU prologue and GroupNorm partials replace the stand-alone passes around the split form),
         // the 1x1 layers on the fp16 GEMM; what they do not take (the stride-2 convs) stays on the split GEMM
-        if (m.linear_math == 2 && split3 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
-        if (m.linear_math == 2 && split1 && femasr_gemm_f16_shape_ok(&a)) return CONV_GEMM_F16;
+        if (m.linear_math == FEMASR_LINEAR_MATH_FP16 && split3 && femasr_conv_f16_shape_ok(&a)) return CONV_F16;
+        if (m.linear_math == FEMASR_LINEAR_MATH_FP16 && split1 && femasr_gemm_f16_shape_ok(&a)) return CONV_GEMM_F16;
         if (split3 || split1) return CONV_SPLIT;
     }
     return CONV_DIRECT;
 }
 
-// Fused GroupNorm partial moments a conv of this form writes when its output feeds a GroupNorm: tiles per sample, 0 = none (the
-// GroupNorm then runs the stand-alone moments kernel, which gives the same coefficients bit for bit).
-int gn_tiles(ConvForm f, const femasr_conv_args &a)
-{
-    const bool fusable = femasr_gn_fusable(a.Cout);
-    switch (f) {
-    case CONV_SPLIT:
-    case CONV_GEMM_F16: return 0;
-    case CONV_BF16X3:
-    case CONV_F16: return fusable && a.Cout <= 256 ? ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16) : 0;       // <= 8 channels per group
-    case CONV_WINO:
-    case CONV_WINO_UP2: return femasr_conv_halo_eligible(&a) && fusable ? femasr_conv_wino_gn_tiles(a.Ho, a.Wo) : 0;      // per 16x16-pixel sub-block
-    default:       // halo kernels: per 8x16 tile; an x2 conv (phase filters) per half-resolution tile and phase
-        if (!femasr_conv_halo_eligible(&a) || !fusable) return 0;
-        return a.up2 ? 4 * ((a.H + 7) / 8) * ((a.W + 15) / 16) : ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-    }
-}
-
-// The forms a conv / linear layer can take under any mode.  conv_form on the layer at a small size, stride 1, no prologue, no
-// activation and the default Winograd limits: every eligibility helper that accepts some call of the layer accepts this one (stride 2,
-// a prologue, an activation or a size limit only ever narrow the choice, and the last falls back to the direct form).
+// The forms a conv / linear layer can take under the modes the handle has ever selected (femasr_handle::decoder_seen / linear_seen):
+// conv_form on the layer at a small size and its real stride, no prologue, no activation and the default Winograd limits.  Every
+// eligibility helper that accepts some call of the layer accepts this one: a prologue, an activation or a size limit only ever narrow
+// the choice, and the last falls back to the direct form.  (Probing at the real stride gives the stride-1 layers - all but the encoder's
+// down convs - what a stride-1 probe gives; a down conv is in front of every lookup, where the only rule that reads the stride before the
+// fp16 modes join is the split 3x3 form's, which takes stride 1 and 2 alike: the same set again.  Once FEMASR_LINEAR_MATH_FP16 has
+// joined, the fp16 halo rule refuses stride 2, so a down conv never gains an fp16 image it cannot use.  No rule reads Ho / Wo.)
 std::array<bool, CONV_FORM_COUNT> layer_forms(const femasr_handle *h, const WSpec &w)
 {
     femasr_conv_args a{};
     a.B = 1; a.H = 16; a.W = 16; a.Cin = (int)w.shape[1]; a.Cout = (int)w.shape[0];
-    a.ksz = w.kind == W_CONV ? (int)w.shape[2] : 1; a.stride = 1; a.pad = a.ksz / 2; a.up2 = w.up2;
+    a.ksz = w.ksz(); a.stride = w.stride; a.pad = a.ksz / 2; a.up2 = w.up2;
+    a.Ho = a.up2 ? 32 : 16 / a.stride; a.Wo = a.Ho;
     std::array<bool, CONV_FORM_COUNT> can{};
+    can[CONV_DIRECT] = true;        // conv_form's last resort; the late images are built from it (ConvFormDesc::from_packed)
     ConvModes m;
-    for (m.decoder_math = 0; m.decoder_math <= 3; ++m.decoder_math)
-        for (m.linear_math = 0; m.linear_math <= 1; ++m.linear_math) can[conv_form(h, m, w.key, a)] = true;
+    for (m.decoder_math = 0; m.decoder_math < FEMASR_DECODER_MATH_COUNT; ++m.decoder_math)
+        for (m.linear_math = 0; m.linear_math < FEMASR_LINEAR_MATH_COUNT; ++m.linear_math)
+            if ((h->decoder_seen >> m.decoder_math & 1) && (h->linear_seen >> m.linear_math & 1)) can[conv_form(h, m, w.key, a)] = true;
     return can;
 }
 
-// The fp16 weight image the layer needs under the selected fp16 modes: 0 = none, 3 = the 3x3 image (CONV_F16), 1 = the k1 image
-// (CONV_GEMM_F16).  dec: decoder_math 4 (the convs behind every lookup), lin: linear_math 2 (the layers in front of one) - disjoint sets, so a
-// layer's image is built once whichever modes are on.  Kept out of layer_forms on purpose: a handle that never selects such a mode allocates
-// and packs nothing for it (femasr_set_decoder_math / femasr_set_linear_math build the images on the first selection, femasr_set_weight
-// keeps them current from then on).
-int layer_f16_image(const femasr_handle *h, const WSpec &w, bool dec, bool lin)
+// Builds every image that a set weight should have (layer_forms) and lacks: the first selection of a mode (femasr_set_weight keeps the
+// images current from then on).  The torch tensors are long gone, so the image comes from the layer's fp32 image - the same values in the
+// same K order, the same bits; only forms with such a repack ever join late.
+int build_missing_images(femasr_handle *h, const char *who)
 {
-    if (w.kind != W_CONV && w.kind != W_LINEAR) return 0;
-    femasr_conv_args a{};
-    a.B = 1; a.H = 16; a.W = 16; a.Cin = (int)w.shape[1]; a.Cout = (int)w.shape[0];
-    a.ksz = w.kind == W_CONV ? (int)w.shape[2] : 1; a.stride = w.stride; a.pad = a.ksz / 2; a.up2 = w.up2;
-    a.Ho = a.up2 ? 32 : 16 / a.stride; a.Wo = a.Ho;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (!(pass == 0 ? dec : lin)) continue;
-        ConvModes m;
-        m.decoder_math = pass == 0 ? 4 : 0;
-        m.linear_math = pass == 0 ? 1 : 2;
-        const ConvForm f = conv_form(h, m, w.key, a);
-        if (f == CONV_F16) return 3;
-        if (f == CONV_GEMM_F16) return 1;
+    DeviceGuard guard(h->cfg.device);
+    FEMASR_REQUIRE(guard.ok, "%s: hipSetDevice(%d) failed", who, h->cfg.device);
+    for (auto &w : h->specs) {
+        if (!w.set || (w.kind != W_CONV && w.kind != W_LINEAR)) continue;
+        const std::array<bool, CONV_FORM_COUNT> can = layer_forms(h, w);
+        for (int f = 0; f < CONV_FORM_COUNT; ++f) {
+            if (!can[f] || w.image[f]) continue;
+            const ConvFormDesc &d = femasr_conv_form_desc(f);
+            assert(d.from_packed);
+            FEMASR_CHECK_HIP(hipMalloc(&w.image[f], d.image_bytes((int)w.shape[0], (int)w.shape[1], w.ksz())));
+            FEMASR_CHECK(d.from_packed(nullptr, w.dev(), (int)w.shape[0], (int)w.shape[1], w.image[f]));
+        }
     }
-    return 0;
-}
-
-// (re)builds the layer's fp16 image `kind` (layer_f16_image) from the torch-layout tensor, or - oihw == nullptr - from the handle's fp32 image
-// of the same values (the first selection of a mode: the torch tensors are long gone); both give the same bits
-int pack_f16_image(WSpec &w, int kind, const float *oihw)
-{
-    const int O = (int)w.shape[0], I = (int)w.shape[1];
-    if (!w.f16) FEMASR_CHECK_HIP(hipMalloc(&w.f16, kind == 3 ? femasr_packed_weight_f16_bytes(O, I, 3, 3) : femasr_packed_weight_k1_f16_bytes(O, I)));
-    if (kind == 3) return oihw ? femasr_repack_oihw_f16(nullptr, oihw, O, I, 3, 3, w.f16) : femasr_repack_packed_f16(nullptr, w.dev, O, I, w.f16);
-    return oihw ? femasr_repack_k1_f16(nullptr, oihw, O, I, w.f16) : femasr_repack_packed_k1_f16(nullptr, w.dev, O, I, w.f16);
+    FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
+    return FEMASR_OK;
 }
 
 // ---------------------------------------------------------------- forward-time helpers
@@ -468,7 +446,7 @@ struct Ctx {
         if (it == h->index.end()) { if (!rc) rc = femasr_set_error(FEMASR_ERR_WEIGHT, "internal: unknown weight %s", key.c_str()); return nullptr; }
         return &h->specs[it->second];
     }
-    const float *Wt(const std::string &key) { const WSpec *w = spec(key); return w ? w->dev : nullptr; }
+    const float *Wt(const std::string &key) { const WSpec *w = spec(key); return w ? w->dev() : nullptr; }
     float *alloc_f(size_t n)
     {
         void *p = arena->alloc(n * sizeof(float));
@@ -515,7 +493,8 @@ struct Ctx {
             rc = femasr_set_error(FEMASR_ERR_INVALID, "conv %s: a second input was scheduled for a conv that does not run in the x2 Winograd-type form", prefix.c_str());
         // the split 3x3 form applies a GroupNorm + SiLU prologue as a pass of its own (exact SiLU: these convs feed the lookup)
         float *act_tmp = (f == CONV_SPLIT && o.pro == FEMASR_PRO_GN_SILU) ? alloc_f(x.numel()) : nullptr;
-        if (o.want_gn && (y.gn_tiles = gn_tiles(f, a)) > 0) {
+        const ConvFormDesc &form = femasr_conv_form_desc(f);
+        if (o.want_gn && form.gn_tiles && (y.gn_tiles = form.gn_tiles(&a)) > 0) {
             y.gn_part = (double *)arena->alloc((size_t)x.B * y.gn_tiles * 32 * 2 * sizeof(double));
             if (!y.gn_part && !rc) rc = femasr_set_error(FEMASR_ERR_WORKSPACE, "workspace too small");
         }
@@ -523,19 +502,11 @@ struct Ctx {
         const WSpec *w = spec(prefix + ".weight");
         a.bias = Wt(prefix + ".bias");
         if (rc) { release(act_tmp); return y; }
-        a.w = w->dev; a.gn_part = y.gn_part;
+        a.w = w->dev(); a.gn_part = y.gn_part;
         if (o.up2) a.w_up2 = w->up2w;
-        const void *image = a.w;
-        switch (f) {
-        case CONV_BF16X3: image = a.w_bf16x3 = w->bf16x3; break;
-        case CONV_F16:
-        case CONV_GEMM_F16: image = a.w_f16 = w->f16; break;
-        case CONV_WINO:
-        case CONV_WINO_UP2: image = a.w_wino = w->wino; a.fast_act = h->modes.decoder_math == 0 ? 1 : 0; break;
-        case CONV_SPLIT: image = a.w_bf16s = w->bf16s; break;
-        default: break;
-        }
-        if (!image) {       // (femasr_set_weight packs the images of every form layer_forms allows)
+        femasr_conv_form_set_image(f, &a, w->image[f]);
+        if (f == CONV_WINO || f == CONV_WINO_UP2) a.fast_act = h->modes.decoder_math == FEMASR_DECODER_MATH_FP32 ? 1 : 0;
+        if (!w->image[f]) {       // (femasr_set_weight packs the images of every form layer_forms allows)
             rc = femasr_set_error(FEMASR_ERR_WEIGHT, "internal: conv %s: the weights of its form %d were not packed", prefix.c_str(), (int)f);
             release(act_tmp);
             return y;
@@ -953,8 +924,11 @@ int femasr_create(const femasr_config *cfg, femasr_handle **out)
     if (rc) { delete h; return rc; }
     // profile slots: the small-kernel families, then every variant of every conv form in ConvForm order (femasr_conv_form_launch)
     for (int i = 0; i < SLOT_SMALL_COUNT; ++i) h->slot_names.push_back(kSmallNames[i]);
-    for (int f = 0; f < CONV_FORM_COUNT; ++f)
-        for (int v = 0; v < femasr_conv_form_variant_count((ConvForm)f); ++v) h->slot_names.push_back(femasr_conv_form_variant_name((ConvForm)f, v));
+    for (int f = 0; f < CONV_FORM_COUNT; ++f) {
+        const ConvFormDesc &d = femasr_conv_form_desc(f);
+        assert(d.form == f);
+        for (int v = 0; v < d.variant_count(); ++v) h->slot_names.push_back(d.variant_name(v));
+    }
     const size_t nslots = h->slot_names.size();
     h->acc_ms.assign(nslots, 0.0); h->acc_flops.assign(nslots, 0.0); h->acc_bytes.assign(nslots, 0.0); h->acc_n.assign(nslots, 0);
     *out = h;
@@ -964,8 +938,10 @@ int femasr_create(const femasr_config *cfg, femasr_handle **out)
 void femasr_destroy(femasr_handle *h)
 {
     if (!h) return;
-    for (auto &w : h->specs)
-        for (void *p : {(void *)w.dev, (void *)w.up2w, w.bf16x3, (void *)w.wino, w.bf16s, w.f16}) if (p) (void)hipFree(p);
+    for (auto &w : h->specs) {
+        for (void *p : w.image) if (p) (void)hipFree(p);
+        if (w.up2w) (void)hipFree(w.up2w);
+    }
     for (int q = 0; q < FEMASR_MAX_CODEBOOKS; ++q) {
         if (h->cbT[q]) (void)hipFree(h->cbT[q]);
         if (h->ee[q]) (void)hipFree(h->ee[q]);
@@ -1006,32 +982,21 @@ int femasr_set_weight(femasr_handle *h, const char *key, const float *dev_ptr, c
     for (int i = 0; same && i < ndim; ++i) same = (shape[i] == w.shape[i]);
     if (!same) return femasr_set_error(FEMASR_ERR_WEIGHT, "set_weight: shape mismatch for '%s'", key);
     if (w.kind != W_CONV && w.kind != W_LINEAR) {
-        if (!w.dev) FEMASR_CHECK_HIP(hipMalloc((void **)&w.dev, w.numel() * sizeof(float)));
-        FEMASR_CHECK_HIP(hipMemcpyAsync(w.dev, dev_ptr, w.numel() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        if (!w.dev()) FEMASR_CHECK_HIP(hipMalloc(&w.image[CONV_DIRECT], w.numel() * sizeof(float)));
+        FEMASR_CHECK_HIP(hipMemcpyAsync(w.dev(), dev_ptr, w.numel() * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
     } else {        // conv / linear: the weights of every form the layer can take
-        const int O = (int)w.shape[0], I = (int)w.shape[1], kk = w.kind == W_CONV ? (int)w.shape[2] : 1;      // (square kernels)
+        const int O = (int)w.shape[0], I = (int)w.shape[1];
         const std::array<bool, CONV_FORM_COUNT> can = layer_forms(h, w);
-        if (!w.dev) FEMASR_CHECK_HIP(hipMalloc((void **)&w.dev, femasr_packed_weight_floats(O, I, kk, kk) * sizeof(float)));
-        int rc = femasr_repack_oihw(nullptr, dev_ptr, O, I, kk, kk, w.dev);                  // CONV_DIRECT (every layer)
-        if (!rc && w.up2 && femasr_up2_weight_floats(O, I)) {       // ... of an x2 conv on the halo kernels: its phase matrices too
+        for (int f = 0; f < CONV_FORM_COUNT; ++f) {
+            if (!can[f]) continue;
+            const ConvFormDesc &d = femasr_conv_form_desc(f);
+            if (!w.image[f]) FEMASR_CHECK_HIP(hipMalloc(&w.image[f], d.image_bytes(O, I, w.ksz())));
+            FEMASR_CHECK(d.repack(dev_ptr, O, I, w.ksz(), w.image[f]));
+        }
+        if (w.up2 && femasr_up2_weight_floats(O, I)) {       // an x2 conv on the halo kernels (CONV_DIRECT): its phase matrices too
             if (!w.up2w) FEMASR_CHECK_HIP(hipMalloc((void **)&w.up2w, femasr_up2_weight_floats(O, I) * sizeof(float)));
-            rc = femasr_repack_oihw_up2(nullptr, dev_ptr, O, I, w.up2w);
+            FEMASR_CHECK(femasr_repack_oihw_up2(nullptr, dev_ptr, O, I, w.up2w));
         }
-        if (!rc && can[CONV_BF16X3]) {
-            if (!w.bf16x3) FEMASR_CHECK_HIP(hipMalloc(&w.bf16x3, femasr_packed_weight_bf16x3_bytes(O, I, 3, 3)));
-            rc = femasr_repack_oihw_bf16x3(nullptr, dev_ptr, O, I, 3, 3, w.bf16x3);
-        }
-        if (!rc)        // only once an fp16 mode that takes the layer has been selected
-            if (const int kind = layer_f16_image(h, w, h->f16_images, h->f16_front_images)) rc = pack_f16_image(w, kind, dev_ptr);
-        if (!rc && (can[CONV_WINO] || can[CONV_WINO_UP2])) {
-            if (!w.wino) FEMASR_CHECK_HIP(hipMalloc((void **)&w.wino, (w.up2 ? femasr_wino_up2_weight_floats(O, I) : femasr_wino_weight_floats(O, I)) * sizeof(float)));
-            rc = w.up2 ? femasr_repack_oihw_wino_up2(nullptr, dev_ptr, O, I, w.wino) : femasr_repack_oihw_wino(nullptr, dev_ptr, O, I, w.wino);
-        }
-        if (!rc && can[CONV_SPLIT]) {       // the three bf16 planes of the (K x Cout) matrix: K = Cin (1x1 / nn.Linear) or 9 Cin (3x3)
-            if (!w.bf16s) FEMASR_CHECK_HIP(hipMalloc(&w.bf16s, kk == 1 ? femasr_packed_weight_bf16s_bytes(O, I) : femasr_packed_weight_conv3x3_bf16s_bytes(O, I)));
-            rc = kk == 1 ? femasr_repack_k1_bf16s(nullptr, dev_ptr, O, I, w.bf16s) : femasr_repack_oihw_bf16s(nullptr, dev_ptr, O, I, w.bf16s);
-        }
-        if (rc) return rc;
     }
     FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
     w.set = true;
@@ -1050,7 +1015,7 @@ int femasr_finalize_weights(femasr_handle *h)
         const int n_e = h->cfg.n_e[q], D = h->cfg.e_dim[q];
         if (!h->cbT[q]) FEMASR_CHECK_HIP(hipMalloc((void **)&h->cbT[q], femasr_packed_weight_floats(n_e, D, 1, 1) * sizeof(float)));
         if (!h->ee[q]) FEMASR_CHECK_HIP(hipMalloc((void **)&h->ee[q], (size_t)n_e * sizeof(float)));
-        const float *cb = h->specs[h->index["quantize_group." + std::to_string(q) + ".embedding.weight"]].dev;
+        const float *cb = h->specs[h->index["quantize_group." + std::to_string(q) + ".embedding.weight"]].dev();
         int rc = femasr_repack_oihw(nullptr, cb, n_e, D, 1, 1, h->cbT[q]);     // packed z.e^T operand
         if (rc) return rc;
         rc = femasr_row_sqsum(nullptr, cb, n_e, D, h->ee[q]);
@@ -1263,19 +1228,11 @@ int femasr_decode_indices(femasr_handle *h, void *stream, const int64_t *indices
 
 int femasr_set_decoder_math(femasr_handle *h, int mode)
 {
-    FEMASR_REQUIRE(h && mode >= 0 && mode <= 4, "set_decoder_math: mode must be 0 (fp32), 1 (bf16x3), 2 (fp32, direct convs only), 3 (fp32, exact SiLU) or 4 (fp16)");
-    if (mode == 4 && !h->f16_images) {
-        // first selection: the fp16 images of the weights set so far, from their fragment-major fp32 images (the same values in the same
-        // K order as the OIHW tensors, which the handle does not keep); femasr_set_weight maintains them from now on
-        DeviceGuard guard(h->cfg.device);
-        FEMASR_REQUIRE(guard.ok, "set_decoder_math: hipSetDevice(%d) failed", h->cfg.device);
-        for (auto &w : h->specs) {
-            const int kind = layer_f16_image(h, w, true, false);
-            if (!w.set || !kind || layer_f16_image(h, w, false, h->f16_front_images)) continue;      // (the other fp16 mode already keeps it)
-            FEMASR_CHECK(pack_f16_image(w, kind, nullptr));
-        }
-        FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        h->f16_images = true;
+    FEMASR_REQUIRE(h && mode >= 0 && mode < FEMASR_DECODER_MATH_COUNT, "set_decoder_math: mode must be 0 (fp32), 1 (bf16x3), 2 (fp32, direct convs only), 3 (fp32, exact SiLU) or 4 (fp16)");
+    if (!(h->decoder_seen >> mode & 1)) {       // first selection: the images of the forms the mode adds
+        h->decoder_seen |= 1u << mode;
+        const int rc = build_missing_images(h, "set_decoder_math");
+        if (rc) { h->decoder_seen &= ~(1u << mode); return rc; }
     }
     if (h->modes.decoder_math != mode) h->plans.clear();
     h->modes.decoder_math = mode;
@@ -1294,21 +1251,24 @@ int femasr_debug_set_wino_limits(femasr_handle *h, int log2_total, int log2_imag
 
 int femasr_set_linear_math(femasr_handle *h, int mode)
 {
-    FEMASR_REQUIRE(h && mode >= 0 && mode <= 2, "set_linear_math: mode must be 0 (fp32 MFMA chain), 1 (bf16 three-term split) or 2 (fp16, one pass)");
-    if (mode == 2 && !h->f16_front_images) {
-        // first selection: the fp16 image of every layer the mode takes, from the handle's fp32 images (as femasr_set_decoder_math does)
-        DeviceGuard guard(h->cfg.device);
-        FEMASR_REQUIRE(guard.ok, "set_linear_math: hipSetDevice(%d) failed", h->cfg.device);
-        for (auto &w : h->specs) {
-            const int kind = layer_f16_image(h, w, false, true);
-            if (!w.set || !kind || layer_f16_image(h, w, h->f16_images, false)) continue;
-            FEMASR_CHECK(pack_f16_image(w, kind, nullptr));
-        }
-        FEMASR_CHECK_HIP(hipStreamSynchronize(nullptr));
-        h->f16_front_images = true;
+    FEMASR_REQUIRE(h && mode >= 0 && mode < FEMASR_LINEAR_MATH_COUNT, "set_linear_math: mode must be 0 (fp32 MFMA chain), 1 (bf16 three-term split) or 2 (fp16, one pass)");
+    if (!(h->linear_seen >> mode & 1)) {        // (as femasr_set_decoder_math)
+        h->linear_seen |= 1u << mode;
+        const int rc = build_missing_images(h, "set_linear_math");
+        if (rc) { h->linear_seen &= ~(1u << mode); return rc; }
     }
     if (h->modes.linear_math != mode) h->plans.clear();
     h->modes.linear_math = mode;
+    return FEMASR_OK;
+}
+
+int femasr_debug_weight_image_bytes(const femasr_handle *h, int form, size_t *bytes)
+{
+    FEMASR_REQUIRE(h && bytes && form >= 0 && form < CONV_FORM_COUNT, "debug_weight_image_bytes: bad args");
+    *bytes = 0;
+    for (const auto &w : h->specs)
+        if ((w.kind == W_CONV || w.kind == W_LINEAR) && w.image[form])
+            *bytes += femasr_conv_form_desc(form).image_bytes((int)w.shape[0], (int)w.shape[1], w.ksz());
     return FEMASR_OK;
 }
 

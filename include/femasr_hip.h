@@ -372,6 +372,10 @@ int femasr_repack_oihw_bf16s(void *stream, const float *w_oihw, int O, int I, vo
  * the MFMA B fragments of one 16-channel step, 1 KiB per column tile, zero padded in Cout.  Cin % 64 == 0 (bytes: 0 otherwise). */
 size_t femasr_packed_weight_k1_f16_bytes(int O, int I);
 int femasr_repack_k1_f16(void *stream, const float *w_oi, int O, int I, void *out);
+/* The mode values of femasr_set_linear_math / femasr_set_decoder_math (described below), by name. */
+enum { FEMASR_LINEAR_MATH_FP32 = 0, FEMASR_LINEAR_MATH_BF16_SPLIT = 1, FEMASR_LINEAR_MATH_FP16 = 2, FEMASR_LINEAR_MATH_COUNT };
+enum { FEMASR_DECODER_MATH_FP32 = 0, FEMASR_DECODER_MATH_BF16X3 = 1, FEMASR_DECODER_MATH_FP32_DIRECT = 2, FEMASR_DECODER_MATH_FP32_STRICT = 3,
+       FEMASR_DECODER_MATH_FP16 = 4, FEMASR_DECODER_MATH_COUNT };
 /* Arithmetic of the network's 1x1 convs / nn.Linear layers (the Swin qkv / proj / fc1 / fc2 and before_quant) and of the 3x3 convs in front of
  * the codebook lookup:
  * 1 (default, 'bf16_split'): the fp32-grade product on the bf16 matrix pipe described at femasr_conv_args.w_bf16s;

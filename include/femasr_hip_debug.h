@@ -39,6 +39,11 @@ int femasr_conv_small_launch_blocks(int blocks);
  * (tests/test_gpu_fp64_anchor.py). */
 int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *name, int cap);
 
+/* *bytes = the bytes of all weight images the handle holds for conv form `form` (the library's ConvForm order: 0 direct, 1 bf16x3,
+ * 2 Winograd, 3 Winograd x2, 4 split-bf16, 5 fp16 halo, 6 fp16 GEMM; the direct form counts conv / linear layers only, without the x2
+ * phase matrices).  tests/ check with it that an fp16 image exists only once its mode has been selected (tests/test_gpu_weight_images.py). */
+int femasr_debug_weight_image_bytes(const femasr_handle *h, int form, size_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif
