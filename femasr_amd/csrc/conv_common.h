@@ -1,4 +1,5 @@
-// conv_common.h — definitions shared by the conv kernel translation units (kernels_conv.hip, kernels_conv_bf16.hip)
+// conv_common.h — definitions shared by the conv and GEMM kernel translation units: the launch parameters, uniform-base global
+// loads / stores, the epilogue transpose scratch, and the host launcher of the two matrix-core halo forms (device frame: halo_mma.h)
 #pragma once
 #include "common.h"
 
@@ -59,6 +60,19 @@ __device__ __forceinline__ void stg4_u32(float *ubase, unsigned byteoff, f32x4_t
 }
 constexpr int TPITCH = 36;                   // epilogue transpose scratch: 32 rows x 36 floats per wave (16-byte rows)
 constexpr int TSCRATCH = 32 * TPITCH;        // floats per wave
+// matrix-core halo forms (halo_mma.h): the scratch starts 8 KiB past the LDS base, behind the GroupNorm `red` area of the fused partials
+// ([WM][BN][2] doubles, 4 KiB in the widest tilings; HaloFrame asserts it)
+constexpr int HALO_EPI_OFF = 2048;           // floats
+
+// two fp32 -> one dword of two fp16, round to nearest even, clamped to the largest finite half first (a finite input never becomes Inf)
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack_f16(float x0, float x1)
+{
+    x0 = __builtin_fminf(__builtin_fmaxf(x0, -65504.f), 65504.f);
+    x1 = __builtin_fminf(__builtin_fmaxf(x1, -65504.f), 65504.f);
+    const f16x2 h = {(_Float16)x0, (_Float16)x1};
+    return __builtin_bit_cast(unsigned, h);
+}
 
 __device__ __forceinline__ float f4get(const float4 &v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 
@@ -107,7 +121,7 @@ int halo_variant_launch(hipStream_t s, const femasr_conv_args *a, const char *wh
     p.NB = (a->Cout + v.bn - 1) / v.bn;
     FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, v.lds + 40 * 1024));
     size_t lds = v.lds + (a->prologue == FEMASR_PRO_GN_SILU ? (size_t)2 * a->Cin * sizeof(float) : 0);
-    const size_t epi = 8192 + (size_t)(v.threads / 64) * 32 * 36 * sizeof(float);       // epilogue transpose scratch
+    const size_t epi = (HALO_EPI_OFF + (size_t)(v.threads / 64) * TSCRATCH) * sizeof(float);       // epilogue transpose scratch
     if (lds < epi) lds = epi;
     FEMASR_REQUIRE(!a->gn_part || (a->Cout % 32 == 0 && (a->Cout / 32) <= 8 && ((a->Cout / 32) & (a->Cout / 32 - 1)) == 0),
                    "%s: fused GN moments need Cout = 32 * {1, 2, 4, 8} (32 groups, power-of-two channels per group)", who);

@@ -12,7 +12,8 @@
 // i.e. ~1e-5 of the activation scale after accumulation — two orders below the 1e-3 bound (measured in
 // tests/test_gpu_kernels.py / test_gpu_network.py).  16x the fp32 MFMA rate / 3 passes = 5.3x per K-step.
 //
-// Structure = conv3x3_halo (kernels_conv.hip): 8x16 output pixels x BN channels per block, one halo patch per
+// Structure = conv3x3_halo (kernels_conv.hip), with the frame of halo_mma.h that the fp16 kernel shares: 8x16 output pixels x BN
+// channels per block, one halo patch per
 // 32-channel block staged ONCE (GroupNorm-apply + SiLU in fp32, then split) and swept by all 9 taps; weights are
 // pre-split and stored fragment-major by femasr_repack_oihw_bf16x3 ([q][ntile][k-step][hi|lo][lane] x 8 bf16: every
 // wave-level load is one contiguous KiB) and read straight into MFMA operands.
@@ -22,18 +23,13 @@
 //   65..128: 64 x 64 per wave; 33..64: 64 px x 32 ch per wave, SINGLE-buffered patch (4 blocks per CU); <= 32: 32 x 32.
 // The main loop is unconditional straight-line code (9 taps unrolled) so every s_waitcnt is exact; the epilogue
 // transposes tiles through LDS for dwordx4 stores and can emit per-tile GroupNorm partial moments of its output.
-#include "conv_common.h"
+#include "halo_mma.h"
 #include "detmath.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 
 namespace {
-
-constexpr int PPITCH = 40;     // ushorts per patch pixel (32 channels + 8 pad)
 
 __device__ __forceinline__ void split_pair(float x0, float x1, unsigned &hi, unsigned &lo)
 {
@@ -42,24 +38,16 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned &hi, uns
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(r0), "v"(r1));
 }
 
-// SiLU with the hardware exp2 / rcp approximations (1 ulp each): this path is tolerance-based (1e-3 contract, ~1e-5
-// measured), so the 28-instruction bit-reproducible det_silu of the fp32 kernels is not needed here.
-__device__ __forceinline__ float fast_silu(float t)
-{
-    return t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.44269504088896341f));
-}
-
 __device__ __forceinline__ bf16x8 as_bf16x8(const uint4 &v) { return __builtin_bit_cast(bf16x8, v); }
 
 template <int BN, int WM, int WN, int PRO, bool UP2>
 __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) ? 4 : 2) void conv3x3_halo_bf16x3_kernel(const ConvParams p, const uint4 *__restrict__ wsplit,
                                                                                           double *__restrict__ stats_part)
 {
-    constexpr int BM = 128, TW = 16, NT = WM * WN * 64;
-    constexpr int PH = UP2 ? 6 : 10, PW = UP2 ? 10 : 18, PP = PH * PW;
-    constexpr int PUNITS = (PP * 8 + NT - 1) / NT, PROWS = NT / 8;
-    constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-    static_assert((WM * WN == 4 || WM * WN == 8) && TM >= 1 && TN >= 1, "tile config");
+    using Frame = HaloFrame<BN, WM, WN, UP2>;
+    constexpr int TW = Frame::TW, NT = Frame::NT, PW = Frame::PW, PP = Frame::PP, PUNITS = Frame::PUNITS, PROWS = Frame::PROWS;
+    constexpr int TM = Frame::TM, TN = Frame::TN;
+    static_assert(WM * WN == 4 || WM * WN == 8, "tile config");
     static_assert(PRO != FEMASR_PRO_LN, "no LayerNorm prologue on 3x3 convs");
     static_assert(1 + PUNITS <= 9, "patch slices are spread over taps 1..");
     // ROT: the 128 px x 64 ch wave tile (8 accumulator tiles = 128 registers) leaves no room for the two-deep A-fragment
@@ -77,46 +65,15 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     constexpr int HALF = (PP + 1) * PPITCH;      // ushorts per (buffer, hi|lo) image; pixel PP is a write-only dummy slot
     unsigned short *Ps = smem_u16;               // [2][2][PP][PPITCH]
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB;
-    int tile = L / p.NB;
-    const int tx = tile % p.tilesX;
-    tile /= p.tilesX;
-    const int ty = tile % p.tilesY;
-    const int n = tile / p.tilesY;
-    const int oy0 = ty * 8, ox0 = tx * TW, n0 = nb * BN;
-    const int sy0 = UP2 ? (oy0 >> 1) - 1 : oy0 - 1, sx0 = UP2 ? (ox0 >> 1) - 1 : ox0 - 1;
-
-    const int kq = t & 7;
-    unsigned poff[PUNITS];
-    unsigned pmask = 0;
-#pragma unroll
-    for (int i = 0; i < PUNITS; ++i) {
-        const int pix = (t >> 3) + PROWS * i;
-        const int ppy = pix / PW, ppx = pix - ppy * PW;
-        const int sy = sy0 + ppy, sx = sx0 + ppx;
-        const bool ok = (pix < PP) & (sy >= 0) & (sy < p.H) & (sx >= 0) & (sx < p.W);
-        poff[i] = ok ? (unsigned)((((size_t)n * p.H + sy) * p.W + sx) * p.Cin + 4 * kq) : 0u;
-        pmask |= (ok ? 1u : 0u) << i;
-    }
-
-    // GroupNorm coefficients of this sample: staged once in LDS behind the patch buffers ([2][Cin] floats), read back per
-    // unit at store time (no per-channel-block global loads in the main loop, no registers held across taps)
-    float *gco = reinterpret_cast<float *>(smem_u16 + (SB ? 2 : 4) * HALF);
-    if (PRO == FEMASR_PRO_GN_SILU) {
-        for (int c = t; c < p.Cin; c += NT) {
-            gco[c] = p.pro_a[(size_t)n * p.Cin + c];
-            gco[p.Cin + c] = p.pro_b[(size_t)n * p.Cin + c];
-        }
-    }
+    Frame f(p);        // block decode and patch unit addressing
+    const int t = f.t, lane = f.lane, wave = f.wave, wm = f.wm, wn = f.wn, n = f.n, oy0 = f.oy0, ox0 = f.ox0, n0 = f.n0, kq = f.kq;
+    float *gco = reinterpret_cast<float *>(smem_u16 + (SB ? 2 : 4) * HALF);      // [2][Cin] floats behind the patch buffers
+    if (PRO == FEMASR_PRO_GN_SILU) f.stage_gn(p, gco);
     float4 rp[GS];
     auto load_patch = [&](int cc, int g) {          // group g: units [g*GS, min((g+1)*GS, PUNITS))
 #pragma unroll
         for (int i = 0; i < GS; ++i)
-            if (g * GS + i < PUNITS) rp[i] = ld4(p.in + (size_t)poff[g * GS + i] + (size_t)cc * BK);
+            if (g * GS + i < PUNITS) rp[i] = ld4(p.in + (size_t)f.poff[g * GS + i] + (size_t)cc * BK);
     };
     auto store_patch_unit = [&](int buf, int i, int cc) {
         int pix = (t >> 3) + PROWS * i;
@@ -130,7 +87,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
             v.z = fast_silu(__builtin_fmaf(v.z, ga.z, gb.z));
             v.w = fast_silu(__builtin_fmaf(v.w, ga.w, gb.w));
         }
-        if (!(pmask & (1u << i))) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!(f.pmask & (1u << i))) v = make_float4(0.f, 0.f, 0.f, 0.f);
         unsigned h01, l01, h23, l23;
         split_pair(v.x, v.y, h01, l01);
         split_pair(v.z, v.w, h23, l23);
@@ -211,21 +168,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     }
     const int koff = 8 * (lane >> 5);                // this lane's k sub-block inside a 16-deep k-step
 
-    // LDS index of this lane's A-fragment pixel for (tap, row tile i).  Without the fused x2 upsample it is ONE per-lane
-    // base plus a compile-time constant (folded into the ds_read offset field); with it the halving depends on the lane.
-    const int abase = (py[0] * PW + px) * PPITCH;
-    auto patch_idx = [&](int tap, int (&idx)[TM]) {
-        const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if (UP2) {
-                const int prow = ((py[i] + ky - 1) >> 1) + 1, pcol = ((px + kx - 1) >> 1) + 1;
-                idx[i] = (prow * PW + pcol) * PPITCH;
-            } else {
-                idx[i] = abase + ((2 * i + ky) * PW + kx) * PPITCH;
-            }
-        }
-    };
+    const int abase = (py[0] * PW + px) * PPITCH;      // LDS index of the fragment pixel of row tile 0 (Frame::patch_idx)
 
     // Main loop.  Everything inside is UNCONDITIONAL straight-line code (9 taps unrolled; the last channel block
     // re-stages itself into the idle LDS buffer and re-reads the last weight chunk) so that the compiler knows exactly
@@ -254,7 +197,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
         if constexpr (ROT) {
             uint4 a_hi[TM], a_lo[TM];
             int aidx[TM], nidx[TM];
-            patch_idx(0, aidx);
+            Frame::patch_idx(0, py, px, abase, aidx);
 #pragma unroll
             for (int i = 0; i < TM; ++i) a_hi[i] = *reinterpret_cast<const uint4 *>(Pb + aidx[i]);
 #pragma unroll
@@ -262,7 +205,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
                 const int q1 = cc * 9 + tap + 1;
                 const size_t qn = (size_t)(q1 < nq ? q1 : nq - 1);
                 if (tap == 0) load_patch(ccn, 0);
-                patch_idx(tap < 8 ? tap + 1 : 8, nidx);
+                Frame::patch_idx(tap < 8 ? tap + 1 : 8, py, px, abase, nidx);
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
 #pragma unroll
@@ -314,7 +257,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
         } else {
             uint4 a_hi[2][TM], a_lo[2][TM];
             int aidx[TM];
-            patch_idx(0, aidx);
+            Frame::patch_idx(0, py, px, abase, aidx);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 a_hi[0][i] = *reinterpret_cast<const uint4 *>(Pb + aidx[i]);
@@ -326,7 +269,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
                 const size_t qn = (size_t)(q1 < nq ? q1 : nq - 1);
                 if (tap == 0) load_patch(ccn, 0);
                 int nidx[TM];
-                patch_idx(tap < 8 ? tap + 1 : 8, nidx);
+                Frame::patch_idx(tap < 8 ? tap + 1 : 8, py, px, abase, nidx);
                 // A fragments are fetched one k-step ahead (s=1 while s=0 multiplies, the next tap's s=0 while s=1
                 // multiplies), pinned with sched_barrier so the LDS latency hides behind MFMAs
 #pragma unroll
@@ -382,7 +325,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
     }
 
     // ---- epilogue.  Stores are ISSUE-bound (one dword store per accumulator register = 256 B per wave instruction), so
-    // each 32x32 tile is transposed through a per-wave LDS scratch (pitch 36 floats: 16-byte rows, conflict-free both
+    // each 32x32 tile is transposed through a per-wave LDS scratch (pitch TPITCH floats: 16-byte rows, conflict-free both
     // ways) and written with dwordx4 stores: lane l holds channels 4(l&7)..+3 of pixel rows (l>>3) + 8k, k = 0..3, i.e.
     // 8 full 128-byte rows per instruction and 4x fewer store instructions.  Needs Cout % 4 == 0 (all layers but the
     // 3-channel out_conv, which keeps the scalar stores).
@@ -411,7 +354,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
             colsq[i][j] = pss;
         }
     if ((p.Cout & 3) == 0) {
-        float *T = reinterpret_cast<float *>(smem_u16) + 2048 + wave * (32 * 36);      // 8 KB in: clear of the GN `red` area
+        float *T = reinterpret_cast<float *>(smem_u16) + HALO_EPI_OFF + wave * TSCRATCH;      // clear of the GN `red` area
         const int trow = lane >> 3, tq = lane & 7;
         const unsigned lvec4 = 4u * ((unsigned)trow * (unsigned)p.Cout + 4u * (unsigned)tq);      // bytes
 #pragma unroll
@@ -419,16 +362,16 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 36 + (lane & 31)] = acc[i][j][r];
+                for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * TPITCH + (lane & 31)] = acc[i][j][r];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float4 v = *reinterpret_cast<const float4 *>(T + (trow + 8 * k) * 36 + 4 * tq);
+                    const float4 v = *reinterpret_cast<const float4 *>(T + (trow + 8 * k) * TPITCH + 4 * tq);
                     const int prow = 2 * (wm * TM + i) + (k >> 1), pcol0 = 8 * (k & 1);               // uniform
                     const bool okv = full || ((oy0 + prow) < p.Ho && (ox0 + pcol0 + trow) < p.Wo && (n0 + (wn * TN + j) * 32 + 4 * tq) < p.Cout);
                     if (okv) {
                         float *ub = p.out + obase + (size_t)(prow * p.Wo + pcol0) * p.Cout + (wn * TN + j) * 32;
                         const unsigned long long a = uniform_u64(reinterpret_cast<unsigned long long>(ub));
-                        *reinterpret_cast<__attribute__((address_space(1))) f32x4 *>(a + lvec4) = f32x4{v.x, v.y, v.z, v.w};
+                        *reinterpret_cast<__attribute__((address_space(1))) f32x4_t *>(a + lvec4) = f32x4_t{v.x, v.y, v.z, v.w};
                     }
                 }
             }
@@ -442,44 +385,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 8 || (BN <= 64 && !UP2)) 
                     if (ok_l(i, j, r)) stg_u32(p.out + uoff(i, j, r), loff4, acc[i][j][r]);
     }
 
-    // Optional fused GroupNorm moments of the output (consumed by the NEXT conv's GN prologue): per (tile, group)
-    // partial sums, reduced lane -> group (xor shuffles over the cg lanes of a group, then the two row halves) -> waves
-    // (LDS) and written as doubles to stats_part[((n*tiles + tile)*32 + g)*2]; a fixed order, so runs are reproducible.
-    if (stats_part) {
-        const int cg = p.Cout >> 5;                       // channels per group (32 groups): 8 / 4 / 2
-        double *red = reinterpret_cast<double *>(smem_u16);   // [WM][BN][2] (patch buffers are dead after the last barrier)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            double s_ = 0.0, q_ = 0.0;      // cross-lane / cross-wave part in fp64 (per-lane partials are <= 32 fp32 terms)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) { s_ += (double)colsum[i][j]; q_ += (double)colsq[i][j]; }
-            for (int sft = 1; sft < cg; sft <<= 1) {
-                s_ += __shfl_xor(s_, sft, 64);
-                q_ += __shfl_xor(q_, sft, 64);
-            }
-            s_ += __shfl_xor(s_, 32, 64);
-            q_ += __shfl_xor(q_, 32, 64);
-            if (lane < 32 && (lane % cg) == 0) {
-                const int gl = ((wn * TN + j) * 32 + lane) / cg;        // group index inside this block's BN columns
-                red[(wm * BN + gl) * 2] = s_;
-                red[(wm * BN + gl) * 2 + 1] = q_;
-            }
-        }
-        __syncthreads();
-        const int ngl = BN / cg;                                         // groups covered by this block
-        if (t < ngl && n0 + t * cg < p.Cout) {
-            double S = 0.0, Q = 0.0;
-#pragma unroll
-            for (int w2 = 0; w2 < WM; ++w2) {
-                S += red[(w2 * BN + t) * 2];
-                Q += red[(w2 * BN + t) * 2 + 1];
-            }
-            const int g = n0 / cg + t;
-            const size_t tile_id = (size_t)n * p.tilesX * p.tilesY + (size_t)ty * p.tilesX + tx;
-            stats_part[(tile_id * 32 + g) * 2] = S;
-            stats_part[(tile_id * 32 + g) * 2 + 1] = Q;
-        }
-    }
+    f.gn_partials(p, colsum, colsq, stats_part, smem_u16);
 }
 
 // OIHW fp32 -> split bf16 fragment-major: out ushort index = (((((q*NT32 + ntile)*2 + s)*2 + h)*64 + lane)*8 + e)

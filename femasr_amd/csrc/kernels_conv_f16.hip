@@ -13,10 +13,10 @@
 //   products t16 * w16 are exact in fp32 (11 + 11 significand bits), accumulated in fp32 by v_mfma_f32_32x32x16_f16;
 //   bias and residuals are added in fp32 (the accumulators start from them); activations stay fp32 in memory.
 //
-// Structure = the bf16x3 kernel's: 8x16 output pixels x BN channels per block, one halo patch per 32-channel block staged once
-// and swept by nine taps, fragment-major weights ([q][ntile][k-step][lane] x 8 halves: every wave-level load is one contiguous
-// KiB), branch-free main loop, residual-initialised accumulators, LDS-transposed dwordx4 stores, fused GroupNorm partials.
-// What differs:
+// Structure = the bf16x3 kernel's, on the frame both share (halo_mma.h): 8x16 output pixels x BN channels per block, one halo patch
+// per 32-channel block staged once and swept by nine taps, fragment-major weights ([q][ntile][k-step][lane] x 8 halves: every
+// wave-level load is one contiguous KiB), branch-free main loop, residual-initialised accumulators, LDS-transposed dwordx4 stores,
+// fused GroupNorm partials.  What differs:
 //   * ONE fp16 image per patch buffer (no lo plane): 14.1 KiB per buffer, so EVERY tiling double-buffers its patch - two buffers
 //     (28.3 KiB) are about the epilogue's transpose scratch (26 KiB), which every block needs anyway; the single-buffered
 //     narrow tilings of the bf16x3 kernel have no reason to exist here.
@@ -25,32 +25,12 @@
 //     (Cout > 128), 64 x 64 (65..128), 32 x 64 (33..64); only Cout <= 32 is left with 32 x 32.
 //   * the A fragments of all tilings are fetched one k-step ahead into a second register set (the 128 x 64 tile has room for it
 //     now: 128 accumulator + 32 fragment + 16 weight registers), so there is one main loop, not two.
-#include "conv_common.h"
+#include "halo_mma.h"
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-constexpr int PPITCH = 40;     // halves per patch pixel (32 channels + 8 pad): 80-byte pitch, conflict-free ds_read_b128 per 16 lanes
-
-// two fp32 -> one dword of two fp16, round to nearest even, clamped to the largest finite half first
-__device__ __forceinline__ unsigned pack_f16(float x0, float x1)
-{
-    x0 = __builtin_fminf(__builtin_fmaxf(x0, -65504.f), 65504.f);
-    x1 = __builtin_fminf(__builtin_fmaxf(x1, -65504.f), 65504.f);
-    const f16x2 h = {(_Float16)x0, (_Float16)x1};
-    return __builtin_bit_cast(unsigned, h);
-}
-
-// SiLU with the hardware exp2 / rcp approximations (1 ulp each), the bf16x3 prologue's
-__device__ __forceinline__ float fast_silu(float t)
-{
-    return t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t * -1.44269504088896341f));
-}
 
 __device__ __forceinline__ f16x8 as_f16x8(const uint4 &v) { return __builtin_bit_cast(f16x8, v); }
 
@@ -58,11 +38,10 @@ template <int BN, int WM, int WN, int PRO, bool UP2>
 __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f16_kernel(const ConvParams p, const uint4 *__restrict__ wf16,
                                                                                          double *__restrict__ stats_part)
 {
-    constexpr int BM = 128, TW = 16, NT = WM * WN * 64;
-    constexpr int PH = UP2 ? 6 : 10, PW = UP2 ? 10 : 18, PP = PH * PW;
-    constexpr int PUNITS = (PP * 8 + NT - 1) / NT, PROWS = NT / 8;
-    constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
-    static_assert(WM * WN == 4 && TM >= 1 && TN >= 1, "tile config");
+    using Frame = HaloFrame<BN, WM, WN, UP2>;
+    constexpr int TW = Frame::TW, NT = Frame::NT, PW = Frame::PW, PP = Frame::PP, PUNITS = Frame::PUNITS, PROWS = Frame::PROWS;
+    constexpr int TM = Frame::TM, TN = Frame::TN;
+    static_assert(WM * WN == 4, "tile config");
     static_assert(PRO != FEMASR_PRO_LN, "no LayerNorm prologue on 3x3 convs");
     static_assert(PUNITS <= 8, "patch slices are stored over the last PUNITS taps, after the loads of tap 0");
 
@@ -70,46 +49,14 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
     constexpr int IMG = (PP + 1) * PPITCH;       // halves per buffer; pixel PP is a write-only dummy slot
     unsigned short *Ps = smem_u16;               // [2][PP + 1][PPITCH]
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB;
-    int tile = L / p.NB;
-    const int tx = tile % p.tilesX;
-    tile /= p.tilesX;
-    const int ty = tile % p.tilesY;
-    const int n = tile / p.tilesY;
-    const int oy0 = ty * 8, ox0 = tx * TW, n0 = nb * BN;
-    const int sy0 = UP2 ? (oy0 >> 1) - 1 : oy0 - 1, sx0 = UP2 ? (ox0 >> 1) - 1 : ox0 - 1;
-
-    // patch unit i of this thread: pixel (t >> 3) + PROWS * i, channels 4 * (t & 7) .. + 3 of the channel block.  Pixels outside
-    // the image (and the units past the patch) read element 0 and are zeroed before the store.
-    const int kq = t & 7;
-    unsigned poff[PUNITS];
-    unsigned pmask = 0;
-#pragma unroll
-    for (int i = 0; i < PUNITS; ++i) {
-        const int pix = (t >> 3) + PROWS * i;
-        const int ppy = pix / PW, ppx = pix - ppy * PW;
-        const int sy = sy0 + ppy, sx = sx0 + ppx;
-        const bool ok = (pix < PP) & (sy >= 0) & (sy < p.H) & (sx >= 0) & (sx < p.W);
-        poff[i] = ok ? (unsigned)((((size_t)n * p.H + sy) * p.W + sx) * p.Cin + 4 * kq) : 0u;
-        pmask |= (ok ? 1u : 0u) << i;
-    }
-
-    // GroupNorm coefficients of this sample: staged once in LDS behind the patch buffers ([2][Cin] floats)
-    float *gco = reinterpret_cast<float *>(smem_u16 + 2 * IMG);
-    if (PRO == FEMASR_PRO_GN_SILU) {
-        for (int c = t; c < p.Cin; c += NT) {
-            gco[c] = p.pro_a[(size_t)n * p.Cin + c];
-            gco[p.Cin + c] = p.pro_b[(size_t)n * p.Cin + c];
-        }
-    }
+    Frame f(p);        // block decode and patch unit addressing
+    const int t = f.t, lane = f.lane, wave = f.wave, wm = f.wm, wn = f.wn, n = f.n, oy0 = f.oy0, ox0 = f.ox0, n0 = f.n0, kq = f.kq;
+    float *gco = reinterpret_cast<float *>(smem_u16 + 2 * IMG);      // [2][Cin] floats behind the patch buffers
+    if (PRO == FEMASR_PRO_GN_SILU) f.stage_gn(p, gco);
     float4 rp[PUNITS];
     auto load_patch = [&](int cc) {
 #pragma unroll
-        for (int i = 0; i < PUNITS; ++i) rp[i] = ld4(p.in + (size_t)poff[i] + (size_t)cc * BK);
+        for (int i = 0; i < PUNITS; ++i) rp[i] = ld4(p.in + (size_t)f.poff[i] + (size_t)cc * BK);
     };
     auto store_patch_unit = [&](int buf, int i, int cc) {
         int pix = (t >> 3) + PROWS * i;
@@ -123,7 +70,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
             v.z = fast_silu(__builtin_fmaf(v.z, ga.z, gb.z));
             v.w = fast_silu(__builtin_fmaf(v.w, ga.w, gb.w));
         }
-        if (!(pmask & (1u << i))) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!(f.pmask & (1u << i))) v = make_float4(0.f, 0.f, 0.f, 0.f);
         *reinterpret_cast<uint2 *>(Ps + buf * IMG + pix * PPITCH + 4 * kq) = make_uint2(pack_f16(v.x, v.y), pack_f16(v.z, v.w));
     };
 
@@ -191,21 +138,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
     }
     const int koff = 8 * (lane >> 5);                // this lane's k sub-block inside a 16-deep k-step
 
-    // LDS index of this lane's A-fragment pixel for (tap, row tile i).  Without the fused x2 upsample it is ONE per-lane
-    // base plus a compile-time constant (folded into the ds_read offset field); with it the halving depends on the lane.
-    const int abase = (py[0] * PW + px) * PPITCH;
-    auto patch_idx = [&](int tap, int (&idx)[TM]) {
-        const int ky = tap / 3, kx = tap - ky * 3;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if (UP2) {
-                const int prow = ((py[i] + ky - 1) >> 1) + 1, pcol = ((px + kx - 1) >> 1) + 1;
-                idx[i] = (prow * PW + pcol) * PPITCH;
-            } else {
-                idx[i] = abase + ((2 * i + ky) * PW + kx) * PPITCH;
-            }
-        }
-    };
+    const int abase = (py[0] * PW + px) * PPITCH;      // LDS index of the fragment pixel of row tile 0 (Frame::patch_idx)
 
     const int nq = ncc * 9;
 #pragma unroll
@@ -234,7 +167,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
         const int nbuf = (cc + 1) & 1;
         uint4 af[2][TM];
         int aidx[TM];
-        patch_idx(0, aidx);
+        Frame::patch_idx(0, py, px, abase, aidx);
 #pragma unroll
         for (int i = 0; i < TM; ++i) af[0][i] = *reinterpret_cast<const uint4 *>(Pb + aidx[i]);
 #pragma unroll
@@ -243,7 +176,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
             const size_t qn = (size_t)(q1 < nq ? q1 : nq - 1);
             if (tap == 0) load_patch(ccn);
             int nidx[TM];
-            patch_idx(tap < 8 ? tap + 1 : 8, nidx);
+            Frame::patch_idx(tap < 8 ? tap + 1 : 8, py, px, abase, nidx);
             // A fragments are fetched one k-step ahead (s=1 while s=0 multiplies, the next tap's s=0 while s=1 multiplies),
             // pinned with sched_barrier so the LDS latency hides behind MFMAs: TM ds_read_b128 per TM*TN MFMAs
 #pragma unroll
@@ -276,7 +209,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
         __syncthreads();
     }
 
-    // ---- epilogue (the bf16x3 kernel's).  Each 32x32 tile is transposed through a per-wave LDS scratch (pitch 36 floats) and
+    // ---- epilogue (the bf16x3 kernel's).  Each 32x32 tile is transposed through a per-wave LDS scratch (pitch TPITCH floats) and
     // written with dwordx4 stores: lane l holds channels 4(l&7)..+3 of pixel rows (l>>3) + 8k, k = 0..3.  Needs Cout % 4 == 0;
     // anything else keeps the scalar stores.
     float colsum[TM][TN], colsq[TM][TN];
@@ -304,7 +237,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
             colsq[i][j] = pss;
         }
     if ((p.Cout & 3) == 0) {
-        float *T = reinterpret_cast<float *>(smem_u16) + 2048 + wave * (32 * 36);      // 8 KB in: clear of the GN `red` area
+        float *T = reinterpret_cast<float *>(smem_u16) + HALO_EPI_OFF + wave * TSCRATCH;      // clear of the GN `red` area
         const int trow = lane >> 3, tq = lane & 7;
         const unsigned lvec4 = 4u * ((unsigned)trow * (unsigned)p.Cout + 4u * (unsigned)tq);      // bytes
 #pragma unroll
@@ -312,16 +245,16 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 36 + (lane & 31)] = acc[i][j][r];
+                for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * TPITCH + (lane & 31)] = acc[i][j][r];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float4 v = *reinterpret_cast<const float4 *>(T + (trow + 8 * k) * 36 + 4 * tq);
+                    const float4 v = *reinterpret_cast<const float4 *>(T + (trow + 8 * k) * TPITCH + 4 * tq);
                     const int prow = 2 * (wm * TM + i) + (k >> 1), pcol0 = 8 * (k & 1);               // uniform
                     const bool okv = full || ((oy0 + prow) < p.Ho && (ox0 + pcol0 + trow) < p.Wo && (n0 + (wn * TN + j) * 32 + 4 * tq) < p.Cout);
                     if (okv) {
                         float *ub = p.out + obase + (size_t)(prow * p.Wo + pcol0) * p.Cout + (wn * TN + j) * 32;
                         const unsigned long long a = uniform_u64(reinterpret_cast<unsigned long long>(ub));
-                        *reinterpret_cast<__attribute__((address_space(1))) f32x4 *>(a + lvec4) = f32x4{v.x, v.y, v.z, v.w};
+                        *reinterpret_cast<__attribute__((address_space(1))) f32x4_t *>(a + lvec4) = f32x4_t{v.x, v.y, v.z, v.w};
                     }
                 }
             }
@@ -335,44 +268,7 @@ __global__ __launch_bounds__(WM * WN * 64, BN <= 64 ? 4 : 2) void conv3x3_halo_f
                     if (ok_l(i, j, r)) stg_u32(p.out + uoff(i, j, r), loff4, acc[i][j][r]);
     }
 
-    // Optional fused GroupNorm moments of the output (consumed by the NEXT conv's GN prologue): per (tile, group) partial sums,
-    // reduced lane -> group (xor shuffles over the cg lanes of a group, then the two row halves) -> waves (LDS) and written as
-    // doubles to stats_part[((n*tiles + tile)*32 + g)*2]; a fixed order, so runs are reproducible.
-    if (stats_part) {
-        const int cg = p.Cout >> 5;                       // channels per group (32 groups): 8 / 4 / 2 / 1
-        double *red = reinterpret_cast<double *>(smem_u16);   // [WM][BN][2] (patch buffers are dead after the last barrier)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            double s_ = 0.0, q_ = 0.0;      // cross-lane / cross-wave part in fp64 (per-lane partials are <= 64 fp32 terms)
-#pragma unroll
-            for (int i = 0; i < TM; ++i) { s_ += (double)colsum[i][j]; q_ += (double)colsq[i][j]; }
-            for (int sft = 1; sft < cg; sft <<= 1) {
-                s_ += __shfl_xor(s_, sft, 64);
-                q_ += __shfl_xor(q_, sft, 64);
-            }
-            s_ += __shfl_xor(s_, 32, 64);
-            q_ += __shfl_xor(q_, 32, 64);
-            if (lane < 32 && (lane % cg) == 0) {
-                const int gl = ((wn * TN + j) * 32 + lane) / cg;        // group index inside this block's BN columns
-                red[(wm * BN + gl) * 2] = s_;
-                red[(wm * BN + gl) * 2 + 1] = q_;
-            }
-        }
-        __syncthreads();
-        const int ngl = BN / cg;                                         // groups covered by this block
-        if (t < ngl && n0 + t * cg < p.Cout) {
-            double S = 0.0, Q = 0.0;
-#pragma unroll
-            for (int w2 = 0; w2 < WM; ++w2) {
-                S += red[(w2 * BN + t) * 2];
-                Q += red[(w2 * BN + t) * 2 + 1];
-            }
-            const int g = n0 / cg + t;
-            const size_t tile_id = (size_t)n * p.tilesX * p.tilesY + (size_t)ty * p.tilesX + tx;
-            stats_part[(tile_id * 32 + g) * 2] = S;
-            stats_part[(tile_id * 32 + g) * 2 + 1] = Q;
-        }
-    }
+    f.gn_partials(p, colsum, colsq, stats_part, smem_u16);
 }
 
 // fp32 -> fp16 (RNE) fragment-major: out half index = ((((q*NT32 + ntile)*2 + s)*64 + lane)*8 + e)

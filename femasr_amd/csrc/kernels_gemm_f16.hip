@@ -25,7 +25,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -42,15 +41,6 @@ constexpr int GH_PITCH = 72;                          // halves per staged row (
 constexpr int GH_BUF = 128 * GH_PITCH;                // halves per buffer
 constexpr int GH_LDS_BYTES = 2 * GH_BUF * 2;          // 36 864
 static_assert(4 * TSCRATCH * 4 <= GH_LDS_BYTES, "epilogue scratch overlays the main-loop buffers");
-
-// two fp32 -> one dword of two fp16, round to nearest even, clamped to the largest finite half first (kernels_conv_f16.hip's)
-__device__ __forceinline__ unsigned gh_pack_f16(float x0, float x1)
-{
-    x0 = __builtin_fminf(__builtin_fmaxf(x0, -65504.f), 65504.f);
-    x1 = __builtin_fminf(__builtin_fmaxf(x1, -65504.f), 65504.f);
-    const f16x2 h = {(_Float16)x0, (_Float16)x1};
-    return __builtin_bit_cast(unsigned, h);
-}
 
 template <int ACT, int NRES>
 // (130 VGPRs: three blocks per CU; a bound of four waves per SIMD spills 7 - 9 dwords to scratch, which the build gate refuses)
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmHParams p)
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             *reinterpret_cast<uint2 *>(As + buf * GH_BUF + (sr0 + 16 * i) * GH_PITCH + 4 * kq) =
-                make_uint2(gh_pack_f16(rp[i].x, rp[i].y), gh_pack_f16(rp[i].z, rp[i].w));
+                make_uint2(pack_f16(rp[i].x, rp[i].y), pack_f16(rp[i].z, rp[i].w));
     };
 
     // ---- W fragments of this wave's two column tiles: [k step][n / 32][lane]; tiles past the packed matrix are clamped (never stored)

@@ -124,6 +124,70 @@ def test_kernel_against_the_specification(cuda_device, case):
         run_case(seed + 50, 2, 8, 16, cin, cout, pro=pro, nres=nres, gn=gn)
 
 
+# ---------------------------------------------------------------- the frame the fp16 and bf16x3 kernels share (csrc/halo_mma.h), exactly
+EXACT_SHAPES = [(13, 21, False), (8, 16, False), (7, 11, True), (4, 8, True)]       # two ragged tiles each way / exactly one tile, plain and x2
+
+
+def _int_conv_ref(x, w, up2):
+    """int64 3x3 pad-1 convolution (nearest x2 first if up2) of integer arrays x (B, H, W, Cin) and w (Cout, Cin, 3, 3): (B, Ho, Wo, Cout)."""
+    if up2:
+        x = x.repeat(2, axis=1).repeat(2, axis=2)
+    B, H, W, _ = x.shape
+    xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    out = np.zeros((B, H, W, w.shape[0]), np.int64)
+    for ky in range(3):
+        for kx in range(3):
+            out += xp[:, ky:ky + H, kx:kx + W, :] @ w[:, :, ky, kx].T
+    return out
+
+
+@pytest.mark.parametrize('cout', [32, 48, 64, 128, 256, 3])
+def test_both_forms_are_exact_on_small_integers(cuda_device, cout):
+    """Integer inputs and weights in [-2, 2], integer bias and residuals in [-8, 8], Cin = 64: every operand is exact in fp16 and in bf16
+    (the bf16x3 lo terms are zero) and every partial sum is an integer below 2^24, so BOTH matrix-core halo forms must return the int64
+    convolution exactly - block decode, patch addressing, masks, residual and bias passes, both store paths (Cout = 3 takes the scalar
+    one) - and their fused GroupNorm partials, computed by the same code from identical accumulators, must agree bit for bit."""
+    lib = _lib.load()
+    rng = np.random.default_rng(1000 + cout)
+    cin = 64
+    w = rng.integers(-2, 3, (cout, cin, 3, 3))
+    bias = rng.integers(-8, 9, cout)
+    wt, bt = torch.from_numpy(w.astype(np.float32)).cuda(), torch.from_numpy(bias.astype(np.float32)).cuda()
+    wb = torch.empty(int(lib.femasr_packed_weight_bf16x3_bytes(cout, cin, 3, 3)), dtype=torch.uint8, device='cuda')
+    _lib.check(lib.femasr_repack_oihw_bf16x3(None, _lib.ptr(wt), cout, cin, 3, 3, _lib.ptr(wb)))
+    images = {'f16': _pack_f16(wt), 'bf16x3': wb}
+    gn = cout // 32 in (1, 2, 4, 8) and cout % 32 == 0
+    for H, W, up2 in EXACT_SHAPES:
+        x = rng.integers(-2, 3, (2, H, W, cin))
+        ho, wo = (2 * H, 2 * W) if up2 else (H, W)
+        res = [rng.integers(-8, 9, (2, ho, wo, cout)) for _ in range(2)]
+        conv = _int_conv_ref(x, w, up2)
+        # before anything is launched: no partial sum of any accumulation order leaves the integers fp32 holds exactly
+        assert int((_int_conv_ref(np.abs(x), np.abs(w), up2) + np.abs(bias) + np.abs(res[0]) + np.abs(res[1])).max()) < 2 ** 24
+        xt = torch.from_numpy(x.astype(np.float32)).cuda()
+        rt = [torch.from_numpy(r.astype(np.float32)).cuda() for r in res]
+        tiles = ((ho + 7) // 8) * ((wo + 15) // 16)
+        for nres in (0, 1, 2):
+            ref = conv + bias + sum(res[:nres])
+            parts = {}
+            for form, image in images.items():
+                out = torch.full((2, ho, wo, cout), float('nan'), device='cuda')
+                part = torch.full((2, tiles, 32, 2), float('nan'), dtype=torch.float64, device='cuda') if gn else None
+                a = _args(xt, image, bt, out, up2, None, rt[:nres], part)
+                if form == 'bf16x3':
+                    a.w_f16, a.w_bf16x3 = None, image.data_ptr()
+                slot = _slot(a)
+                assert slot.startswith(f'conv3x3_halo_{form}<'), slot
+                _launch(a)
+                what = f'{slot} {H}x{W}{" up2" if up2 else ""} ->{cout} nres {nres}'
+                assert np.array_equal(out.cpu().numpy().astype(np.float64), ref.astype(np.float64)), what
+                if gn:
+                    assert bool(torch.isfinite(part).all()), what
+                    parts[form] = part
+            if gn:
+                assert torch.equal(parts['f16'], parts['bf16x3']), f'GroupNorm partials differ between the forms: {H}x{W} up2={up2} ->{cout} nres {nres}'
+
+
 def test_subnormal_weights_take_part_with_their_value(cuda_device):
     """Every weight an fp16 SUBNORMAL, |w| in [2^-24, 2^-15], inputs N(0,1) * 64 so the sums are far above the fp32 accumulation's noise:
     the specification says they multiply with their value.  A flush to zero would give bias exactly."""
