@@ -474,22 +474,57 @@ class FeMaSRNet(nn.Module):
         return out, idx
 
     @torch.no_grad()
-    def test_u8(self, img_u8, bgr=False, out=None, color_fix=False):
+    def test_u8(self, img_u8, bgr=False, out=None, color_fix=False, self_ensemble=False):
         """The CLI arithmetic of inference_femasr.py:50-67 on the device in ONE native call: uint8 (H,W,3) or (B,H,W,3) image(s) ->
         uint8 (sH,sW,3) / (B,sH,sW,3); decode (`/255.`) is fused into the forward's mirror-pad kernel and tensor2img (clamp, x255,
         round half to even) into its crop kernel (femasr_forward_u8) - the same bits as imgproc.u8_to_input -> test() ->
         imgproc.output_to_u8, without the two fp32 NCHW images in between.  `out`: a contiguous uint8 (B,sH,sW,3) tensor the crop
         kernel stores into (the tiled / multi-GPU callers pass slices of their result or all-gather send buffers).
         color_fix=True (NOT the reference's arithmetic, off by default): the wavelet colour fix of the result's BYTES against the input's
-        (femasr_amd.colorfix.wavelet_color_fix, `color_fix_levels` levels), in place on the result."""
+        (femasr_amd.colorfix.wavelet_color_fix, `color_fix_levels` levels), in place on the result.
+        self_ensemble=True (NOT the reference's arithmetic, off by default): the x8 geometric self-ensemble (`_ensemble`) of the BYTES of
+        eight `test_u8` results, S / 8 rounded half to even - deliberately not the quantised fp32 ensemble; a colour fix comes after it."""
         if img_u8.device.type != 'cuda':
             raise _lib.FemasrError('test_u8: tensor must be on the GPU (no CPU fallback)')
         x, single = self._u8_batch(img_u8)
-        lib, h = self._native(x.device)
-        out = self._forward_native(lib, h, _U8, x, 1, out, flags=(int(bool(bgr)),), indices=False)[0]
+        if self_ensemble:
+            out = self._ensemble(_U8, functools.partial(self._test_u8, bgr=bgr), x, out)
+        else:
+            out = self._test_u8(x, bgr, out)
         if color_fix:
             self._color_fix(out, x)
         return out[0] if single else out
+
+    def _test_u8(self, x, bgr=False, out=None):
+        """The plain uint8 forward on a contiguous (B,H,W,3) batch."""
+        lib, h = self._native(x.device)
+        return self._forward_native(lib, h, _U8, x, 1, out, flags=(int(bool(bgr)),), indices=False)[0]
+
+    def _test(self, x, out=None):
+        """The plain fp32 forward with test()'s pad / crop geometry."""
+        return self._run(x, 1, out)[0]
+
+    def _ensemble(self, fmt, run, x, out=None):
+        """The opt-in x8 geometric self-ensemble of `run` (the plain `test` / `test_u8`, `run(batch[, out=])`) on the contiguous image batch
+        `x` in tile format `fmt`: expand -> forwards -> merge (femasr_amd/ensemble.py; ONE launch each on the GPU, the torch definition on
+        host tensors - the CPU-side tests of the schedule).  The variants of one shape class ((H,W) and (W,H); ONE class of eight when
+        H == W) run in calls of at most max(1, max_tile_batch // B) whole variants, each writing straight into its place of the result
+        buffers; the result does not depend on that split (the forward is bitwise independent of the batch size).  The
+        merge writes into `out` when one is given."""
+        from .. import ensemble
+        b = fmt.bchw(x)[0]
+        xs, xt = ensemble.expand(x)
+        ys, yt = ensemble.result_buffers(x, self.scale_factor)
+        xa, ya = ensemble.as_batch(xs, xt), ensemble.as_batch(ys, yt)
+        per = max(1, self.max_tile_batch // max(1, b))
+        in_place = _takes_out(run)
+        for src, dst in ([(xa, ya)] if xa is not None and ya is not None else [(xs, ys), (xt, yt)]):
+            for i in range(0, src.shape[0], per):
+                d = dst[i:i + per].flatten(0, 1)
+                y = run(src[i:i + per].flatten(0, 1), out=d) if in_place else run(src[i:i + per].flatten(0, 1))
+                if y.data_ptr() != d.data_ptr():
+                    d.copy_(y)
+        return ensemble.merge(ys, yt, out)
 
     def _color_fix(self, canvas, x):
         """The opt-in wavelet colour fix of a finished result against the whole input, in place (femasr_amd/colorfix.py)."""
@@ -524,14 +559,22 @@ class FeMaSRNet(nn.Module):
         return self.encode_and_decode(input, gt_indices)
 
     @torch.no_grad()
-    def test(self, input, out=None, color_fix=False):
+    def test(self, input, out=None, color_fix=False, self_ensemble=False):
         """femasr_arch.py:449-468: mirror-pad to (h//wsz+1)*wsz, run, crop to (h*s, w*s).  `out` (not in the reference): a
         contiguous float32 (B, 3, h*s, w*s) tensor the result is written INTO by the last kernel of the forward - the tiled /
         multi-GPU callers pass slices of their result or all-gather send buffers, so no copy follows.
         color_fix=True (not in the reference, off by default): the wavelet colour fix of the result against `input`
         (femasr_amd.colorfix.wavelet_color_fix, `color_fix_levels` levels), after the forward - outside the captured graph with
-        `use_graph` - and in place on the result."""
-        y = self._run(input, 1, out)[0]
+        `use_graph` - and in place on the result.
+        self_ensemble=True (not in the reference, off by default): the x8 geometric self-ensemble (`_ensemble`, femasr_amd/ensemble.py,
+        DESIGN.md 18): this forward on the eight flips / transposes of `input`, mapped back and averaged in a fixed fp32 order, at eight
+        times the compute; a colour fix comes after it."""
+        if self_ensemble:
+            if input.dim() != 4 or input.shape[1] != self.in_channel:
+                raise ValueError(f'expected (B,{self.in_channel},H,W), got {tuple(input.shape)}')
+            y = self._ensemble(_FP32, self._test, input.detach().to(torch.float32).contiguous(), out)
+        else:
+            y = self._test(input, out)
         if color_fix:
             self._color_fix(y, input.detach().to(torch.float32).contiguous())
         return y
@@ -561,7 +604,8 @@ class FeMaSRNet(nn.Module):
 
     # ------------------------------------------------------------------ tiled inference
     @torch.no_grad()
-    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False, color_fix=False):
+    def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False, color_fix=False,
+                  self_ensemble=False):
         """Reference semantics of femasr_arch.py:387-447 (overlap-discard paste onto a zero canvas), but
         tiles of one shape class run as batched `test()` calls, and with world_size > 1 each rank
         computes a contiguous share of every class; `gather(results, classes, batch, channel, scale) -> list per rank`
@@ -575,12 +619,16 @@ class FeMaSRNet(nn.Module):
         color_fix=True (NOT the reference's arithmetic either, off by default): after the paste or the blend, on the pasting ranks, the
         wavelet colour fix of the WHOLE canvas against the WHOLE input (femasr_amd/colorfix.py): everything coarser than
         ~2^color_fix_levels pixels comes from the bicubically upsampled input, which knows nothing of tiles - the per-tile tone offsets
-        that `blend` only turns into ramps go away.  Defined on canvas and input alone, so independent of the partition and the ranks."""
-        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste, blend, color_fix)
+        that `blend` only turns into ramps go away.  Defined on canvas and input alone, so independent of the partition and the ranks.
+        self_ensemble=True (NOT the reference's arithmetic, off by default): every tile is the x8 geometric self-ensemble of its crop
+        (`test(crop, self_ensemble=True)`) - per TILE, so the tile grid, the partition, the gather payload, the paste, `blend`
+        and `color_fix` are what they are without it; batched calls hold max_tile_batch // (8 * batch) tiles' worth of variants."""
+        return self._tiled(input.contiguous().float(), _FP32, self.test, tile_size, tile_pad, rank, world_size, gather, paste, blend, color_fix,
+                           self_ensemble)
 
     @torch.no_grad()
     def test_tile_u8(self, img_u8, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, bgr=False, blend=False,
-                     color_fix=False):
+                     color_fix=False, self_ensemble=False):
         """`test_tile` on uint8 images end to end (round 6; the CLI's tiled branch, inference_femasr.py:58-67 with femasr_arch.py:387-447):
         uint8 (H,W,3) / (B,H,W,3) in -> uint8 (sH,sW,3) / (B,sH,sW,3) out.  Tiles are cropped as uint8, every batched call is ONE
         `test_u8` (decode fused into the mirror-pad kernel, tensor2img into the crop kernel, which stores straight into the result /
@@ -590,15 +638,17 @@ class FeMaSRNet(nn.Module):
         blend=True: as in `test_tile`, on the BYTES the tiles hold after tensor2img (the all-gather payload stays one byte per value):
         the weighted mean of the covering windows' bytes, rounded half to even - not tensor2img of the fp32 blend.
         color_fix=True: as in `test_tile`, on the canvas BYTES against the input bytes (planes byte / 255, the result rounded half to even):
-        no fp32 canvas is held, the fix works through the planes in groups of bounded size."""
+        no fp32 canvas is held, the fix works through the planes in groups of bounded size.
+        self_ensemble=True: as in `test_tile`, every tile the ensemble of the BYTES of eight `test_u8` results (S / 8, half to even)."""
         x, single = self._u8_batch(img_u8)
         output = self._tiled(x, _U8, functools.partial(self.test_u8, bgr=bgr), tile_size, tile_pad, rank, world_size, gather, paste, blend,
-                             color_fix)
+                             color_fix, self_ensemble)
         return output[0] if single and output is not None else output
 
-    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste, blend=False, color_fix=False):
+    def _tiled(self, x, fmt, run, tile_size, tile_pad, rank, world_size, gather, paste, blend=False, color_fix=False, self_ensemble=False):
         """The tile schedule of `test_tile` and `test_tile_u8`: `x` is the contiguous image batch in tile format `fmt`,
-        `run(crops[, out=])` the batched call on the crops of one shape class.  Returns the canvas (None with paste=False)."""
+        `run(crops[, out=])` the batched call on the crops of one shape class.  Returns the canvas (None with paste=False).
+        self_ensemble: `run` becomes its x8 ensemble form (`_ensemble`), on an eighth as many tiles per call."""
         if blend:
             tiling.check_blend(tile_size, tile_pad)             # before any work
         batch, channel, height, width = fmt.bchw(x)
@@ -620,6 +670,9 @@ class FeMaSRNet(nn.Module):
             results = {hw: torch.empty(tiling.tile_shape(fmt.dtype, len(tl) * batch, channel, hw[0] * s, hw[1] * s), dtype=fmt.dtype,
                                        device=x.device) for hw, tl in mine.items()}
         per_call = max(1, self.max_tile_batch // batch)
+        if self_ensemble:
+            per_call = max(1, self.max_tile_batch // (8 * batch))
+            run = functools.partial(self._ensemble, fmt, run)
         in_place = _takes_out(run)
         for hw, tl in mine.items():
             for i in range(0, len(tl), per_call):

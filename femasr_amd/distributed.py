@@ -178,7 +178,7 @@ def gather_tiles(results, classes, batch, channel, scale, group=None):
     return _exchange_for(group)(results, classes, batch, channel, scale)
 
 
-def test_tile_parallel(net, x, tile_size=240, tile_pad=16, group=None, root_only=False, blend=False, color_fix=False):
+def test_tile_parallel(net, x, tile_size=240, tile_pad=16, group=None, root_only=False, blend=False, color_fix=False, self_ensemble=False):
     """`net.test_tile` sharded over the process group.  Every rank returns the full upscaled image, or - root_only=True - only
     rank 0 pastes it (the others return None): one canvas write per job instead of one per rank.
     A uint8 image ((H,W,3) / (B,H,W,3), the CLI's data type) takes the uint8 path (`net.test_tile_u8`): tiles are produced, gathered
@@ -186,10 +186,14 @@ def test_tile_parallel(net, x, tile_size=240, tile_pad=16, group=None, root_only
     blend=True: the pasting ranks blend the overlaps instead of discarding them (`FeMaSRNet.test_tile`); the gathered buffers already
     hold whole windows, so the collective's payload is the same, and the canvas does not depend on which rank computed which tile.
     color_fix=True: the pasting ranks run the wavelet colour fix on their finished canvas (`FeMaSRNet.test_tile`); nothing is exchanged
-    for it - every rank holds the whole input."""
+    for it - every rank holds the whole input.
+    self_ensemble=True: every rank's tiles are the x8 geometric self-ensemble of their crops (`FeMaSRNet.test_tile`); the partition and the
+    collective's payload are the same."""
     fn = net.test_tile_u8 if x.dtype == torch.uint8 else net.test_tile
     if color_fix:
         fn = functools.partial(fn, color_fix=True)
+    if self_ensemble:
+        fn = functools.partial(fn, self_ensemble=True)
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
         return fn(x, tile_size, tile_pad, blend=blend)
     ex = _exchange_for(group)

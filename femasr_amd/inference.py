@@ -62,6 +62,9 @@ def build_parser():
                     help='wavelet colour fix of the result: detail from the network, everything coarser than ~2^N pixels from the bicubically '
                          "upsampled input (removes per-tile tone offsets and colour drift; NOT the reference's arithmetic, off by default)")
     ap.add_argument('--color-fix-levels', type=int, default=5, metavar='N', help='levels of --color-fix (1..12, default 5)')
+    ap.add_argument('--self-ensemble', action='store_true',
+                    help='x8 geometric self-ensemble: the network runs on the eight flips / transposes of the image (of every tile on the tiled '
+                         "branch) and the eight results' bytes are averaged, at eight times the compute (NOT the reference's arithmetic, off by default)")
     return ap
 
 
@@ -93,6 +96,8 @@ def main(argv=None):
         raise SystemExit(f'--color-fix-levels must be in 1..12, got {args.color_fix_levels}')
     model.color_fix_levels = args.color_fix_levels
     fix = {'color_fix': True} if args.color_fix else {}
+    if args.self_ensemble:
+        fix['self_ensemble'] = True
     model.num_streams = args.streams          # tiled images run as batched test() calls: sub-batches on internal streams (bit-identical for any split)
     model = model.to(dev).eval()
 

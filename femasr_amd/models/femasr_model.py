@@ -358,6 +358,9 @@ class FeMaSRModel:
         fix = {'color_fix': True} if val.get('color_fix', False) else {}
         if fix and val.get('color_fix_levels') is not None:
             self.net_g.color_fix_levels = int(val['color_fix_levels'])
+        # `val: self_ensemble: true` (an extension key, absent = false): the opt-in x8 geometric self-ensemble on either branch
+        if val.get('self_ensemble', False):
+            fix['self_ensemble'] = True
         if h * w < min_size:
             self.output = self.net_g.test(self.lq, **fix)
         else:

@@ -532,6 +532,24 @@ int femasr_color_fix_u8(void *stream, const uint8_t *sr, const uint8_t *lq, int 
                         const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w, int taps_w, uint8_t *out,
                         void *ws, size_t ws_bytes);
 
+/* ---- x8 geometric self-ensemble (opt-in, femasr_amd.ensemble / FeMaSRNet.test*(..., self_ensemble=True); NOT the reference's arithmetic) ----
+ * The data movement around the eight forwards.  Variant k = 0..7: v = k & 1 flips rows, h = (k >> 1) & 1 flips columns,
+ * t = (k >> 2) & 1 transposes, x_k = T^t(H^h(V^v(x))) per image and channel:
+ *   expand  x (H,W) ->  k = 0..3 (H,W): x_k[i,j] = x[v ? H-1-i : i, h ? W-1-j : j];   k = 4..7 (W,H): x_k[i,j] = x[v ? H-1-j : j, h ? W-1-i : i]
+ *   merge   z_k[i,j] = y_k[v ? H-1-i : i, h ? W-1-j : j] (k = 0..3, y_k of (H,W));   z_k[i,j] = y_k[h ? W-1-j : j, v ? H-1-i : i] (k = 4..7, y_k of
+ *           (W,H));  H, W: the OUTPUT's.  fp32: out = 0.125f * (((((((z_0 + z_1) + z_2) + z_3) + z_4) + z_5) + z_6) + z_7), one IEEE fp32 add per
+ *           step in this order.  uint8: S = sum_k z_k per byte, out = (S + 3 + ((S >> 3) & 1)) >> 3 (S / 8, half to even): the mean of the
+ *           BYTES, not the quantised fp32 mean.
+ * Buffers are variant-major: straight (4,B,C,H,W) / (4,B,H,W,3) holds k = 0..3, transposed (4,B,C,W,H) / (4,B,W,H,3) holds k = 4..7.  With H == W
+ * a caller may pass transposed = straight + 4 B C H W elements and treat all eight variants as one batch.  No buffer of a call may overlap
+ * another otherwise.  One launch per call on `stream`; no atomics, no allocation, no synchronisation (capture-safe); 64-bit offsets.
+ * Refused with FEMASR_ERR_INVALID before any launch: a null pointer, a count or size <= 0, a plane of 2^31 elements or more, more than
+ * 2^31 - 1 tiles of 64x64 in all. */
+int femasr_dihedral_expand(void *stream, const float *x, int B, int C, int H, int W, float *straight, float *transposed);
+int femasr_dihedral_expand_u8(void *stream, const uint8_t *x, int B, int H, int W, uint8_t *straight, uint8_t *transposed);
+int femasr_dihedral_merge(void *stream, const float *straight, const float *transposed, int B, int C, int H, int W, float *out);
+int femasr_dihedral_merge_u8(void *stream, const uint8_t *straight, const uint8_t *transposed, int B, int H, int W, uint8_t *out);
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
