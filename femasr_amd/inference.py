@@ -65,7 +65,59 @@ def build_parser():
     ap.add_argument('--self-ensemble', action='store_true',
                     help='x8 geometric self-ensemble: the network runs on the eight flips / transposes of the image (of every tile on the tiled '
                          "branch) and the eight results' bytes are averaged, at eight times the compute (NOT the reference's arithmetic, off by default)")
+    ap.add_argument('--io-threads', type=int, default=0, metavar='N',
+                    help='0 (default): decode, forward, Image.save one after the other, as ever.  N >= 1 (at most 16): the row filters of '
+                         'PNG run on the GPU, N threads deflate and write behind the forward (femasr_amd.pngio: the same pixels, not the '
+                         'same file bytes), one more thread decodes up to two inputs ahead')
+    ap.add_argument('--png-level', type=int, default=6, metavar='0..9', help="deflate level of --io-threads N >= 1 (default 6, PIL's)")
     return ap
+
+
+def _decode(path):
+    from PIL import Image
+    return np.array(Image.open(path).convert('RGB'))                      # cv2.imread + BGR2RGB == RGB
+
+
+def _decoded(paths, ahead):
+    """(path, RGB array) in order.  ahead = 0: decoded when asked for; else one thread decodes at most `ahead` images ahead."""
+    if not ahead:
+        for path in paths:
+            yield path, _decode(path)
+        return
+    import queue
+    import threading
+    q, stop = queue.Queue(maxsize=ahead), threading.Event()
+
+    def put(item):
+        while not stop.is_set():
+            try:
+                return q.put(item, timeout=0.1)
+            except queue.Full:
+                pass
+
+    def reader():
+        try:
+            for path in paths:
+                if stop.is_set():
+                    return
+                put((path, _decode(path), None))
+            put(None)
+        except BaseException as e:
+            put((None, None, e))
+
+    th = threading.Thread(target=reader, name='decode-ahead', daemon=True)
+    th.start()
+    try:
+        while True:
+            item = q.get()
+            if item is None:
+                return
+            if item[2] is not None:
+                raise item[2]
+            yield item[0], item[1]
+    finally:
+        stop.set()
+        th.join()
 
 
 def main(argv=None):
@@ -92,6 +144,8 @@ def main(argv=None):
         raise SystemExit('no network here: pass -w <weights.pth> (FeMaSR_SRX4/SRX2_model_g.pth) or --synthetic-seed N')
     model.decoder_math = args.decoder_math
     model.linear_math = args.linear_math
+    if args.io_threads < 0 or not 0 <= args.png_level <= 9:
+        raise SystemExit(f'--io-threads must be >= 0 and --png-level in 0..9, got {args.io_threads} and {args.png_level}')
     if not 1 <= args.color_fix_levels <= 12:
         raise SystemExit(f'--color-fix-levels must be in 1..12, got {args.color_fix_levels}')
     model.color_fix_levels = args.color_fix_levels
@@ -104,9 +158,22 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(args.output, exist_ok=True)
     paths = [args.input] if os.path.isfile(args.input) else sorted(glob.glob(os.path.join(args.input, '*')))
-    for path in paths:
+    writer = None
+    if args.io_threads >= 1 and rank == 0:
+        from femasr_amd import pngio
+        writer = pngio.PngWriter(threads=min(args.io_threads, pngio.MAX_THREADS), level=args.png_level)
+    try:
+        _run(args, model, paths, dev, rank, world, fix, writer, fd, Image)
+    finally:
+        if writer is not None:
+            writer.close()
+    if world > 1:
+        torch.distributed.barrier()
+
+
+def _run(args, model, paths, dev, rank, world, fix, writer, fd, Image):
+    for path, rgb in _decoded(paths, 2 if args.io_threads >= 1 else 0):
         img_name = os.path.basename(path)
-        rgb = np.array(Image.open(path).convert('RGB'))                   # cv2.imread + BGR2RGB == RGB
         xu8 = torch.from_numpy(rgb).to(dev)
         h, w = rgb.shape[:2]
         if h * w < args.max_size ** 2:
@@ -119,10 +186,10 @@ def main(argv=None):
                 u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend, **fix)
             else:
                 u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend, **fix)
-        if rank == 0:
+        if writer is not None:
+            writer.submit(u8, os.path.join(args.output, img_name))
+        elif rank == 0:
             Image.fromarray(u8.cpu().numpy(), 'RGB').save(os.path.join(args.output, img_name))
-    if world > 1:
-        torch.distributed.barrier()
 
 
 if __name__ == '__main__':

@@ -378,7 +378,6 @@ class FeMaSRModel:
         return self.nondist_validation(dataloader, current_iter, tb_logger, save_img, save_as_dir)
 
     def nondist_validation(self, dataloader, current_iter, tb_logger, save_img, save_as_dir=None):
-        from PIL import Image
         dataset_name = dataloader.dataset.opt['name']
         val_opt = self.opt.get('val', {}) or {}
         metrics = val_opt.get('metrics') or {}
@@ -397,6 +396,26 @@ class FeMaSRModel:
             logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), niqe needs '
                            '`pretrained_model_path` (a local niqe_pris_params.npz), other pyiqa types are not implemented in this build',
                            skipped)
+        # `val: io_threads: N` (extension key; absent: Image.save here, as ever): the saves go through a pngio.PngWriter - PNG row filters
+        # on the GPU, N threads deflate and write behind the next forward; the same pixels in the files
+        writer = None
+        if save_img and val_opt.get('io_threads'):
+            from .. import pngio
+            writer = pngio.PngWriter(threads=min(int(val_opt['io_threads']), pngio.MAX_THREADS))
+        try:
+            n = self._validate_images(dataloader, dataset_name, val_opt, metrics, save_img, save_as_dir, writer, noref_metrics, pixel_metrics,
+                                      gpu_metrics)
+        finally:
+            if writer is not None:
+                writer.close()                              # every file is written before the metrics are logged
+        for name in self.metric_results:
+            self.metric_results[name] = self.metric_results[name] / max(n, 1) if name not in skipped else None
+        if metrics:
+            logger.info('Validation %s: %s', dataset_name, self.metric_results)
+        return self.metric_results
+
+    def _validate_images(self, dataloader, dataset_name, val_opt, metrics, save_img, save_as_dir, writer, noref_metrics, pixel_metrics, gpu_metrics):
+        from PIL import Image
         n = 0
         for val_data in dataloader:
             img_name = os.path.splitext(os.path.basename(val_data['lq_path'][0]))[0]
@@ -405,14 +424,20 @@ class FeMaSRModel:
             # tensor2img (img_util.py:38-94) on the GPU: clamp / x255 / round-half-even in a HIP kernel; uint8 crosses PCIe only to be saved
             sr_u8 = imgproc.output_to_u8(self.output)
             if save_img:
-                sr_img = sr_u8.cpu().numpy()
                 suffix = val_opt.get('suffix') or self.opt['name']
                 save_img_path = os.path.join(self.opt['path']['visualization'], dataset_name, f'{img_name}_{suffix}.png')
                 os.makedirs(os.path.dirname(save_img_path), exist_ok=True)
-                Image.fromarray(sr_img, 'RGB').save(save_img_path)
                 if save_as_dir:
                     os.makedirs(save_as_dir, exist_ok=True)
-                    Image.fromarray(sr_img, 'RGB').save(os.path.join(save_as_dir, f'{img_name}.png'))
+                if writer is not None:
+                    writer.submit(sr_u8, save_img_path)
+                    if save_as_dir:
+                        writer.submit(sr_u8, os.path.join(save_as_dir, f'{img_name}.png'))
+                else:
+                    sr_img = sr_u8.cpu().numpy()
+                    Image.fromarray(sr_img, 'RGB').save(save_img_path)
+                    if save_as_dir:
+                        Image.fromarray(sr_img, 'RGB').save(os.path.join(save_as_dir, f'{img_name}.png'))
             for name, fn in noref_metrics.items():
                 self.metric_results[name] += fn(sr_u8)
             if metrics and hasattr(self, 'gt'):
@@ -428,11 +453,7 @@ class FeMaSRModel:
             if hasattr(self, 'gt'):
                 del self.gt
             n += 1
-        for name in self.metric_results:
-            self.metric_results[name] = self.metric_results[name] / max(n, 1) if name not in skipped else None
-        if metrics:
-            logger.info('Validation %s: %s', dataset_name, self.metric_results)
-        return self.metric_results
+        return n
 
     def _gpu_metric(self, name, m):
         """The LPIPS module of metric `name` (built once per model and option set)."""

@@ -550,6 +550,20 @@ int femasr_dihedral_expand_u8(void *stream, const uint8_t *x, int B, int H, int 
 int femasr_dihedral_merge(void *stream, const float *straight, const float *transposed, int B, int C, int H, int W, float *out);
 int femasr_dihedral_merge_u8(void *stream, const uint8_t *straight, const uint8_t *transposed, int B, int H, int W, uint8_t *out);
 
+/* ---- PNG row filters (opt-in, femasr_amd.pngio: the GPU stage of the fast PNG output; changes no pixel) ----
+ * img: uint8 (B,H,W,3) -> out: uint8 (B,H,1 + 3W), the byte stream PNG deflates for colour type 2, bit depth 8, no interlace.
+ * Per row y of an image, n = 3W, raw[y] its n bytes, and per byte i with x = raw[y][i]:
+ *   a = raw[y][i-3] (0 if i < 3),  b = raw[y-1][i] (0 if y == 0),  c = raw[y-1][i-3] (0 if either is outside)
+ *   f0 = x,  f1 = x - a,  f2 = x - b,  f3 = x - ((a + b) >> 1),  f4 = x - paeth(a, b, c)   (mod 256)
+ *   paeth: p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|: a if pa <= pb and pa <= pc, else b if pb <= pc, else c
+ *   cost_t = sum_i min(f_t[i], 256 - f_t[i]);   out[y] = [t, f_t[0], ..., f_t[n-1]]
+ * filter = 0..4: t = filter for every row; filter = 5 (adaptive): per row the smallest t of least cost.  Integer work: the result is
+ * bit-identical to femasr_amd.pngio.filter_rows.  img and out need no alignment and must not overlap.  One launch on `stream`; no
+ * workspace, no atomics, no allocation, no synchronisation (capture-safe); 64-bit offsets between rows and images.
+ * Refused with FEMASR_ERR_INVALID before any launch: a null pointer, B, H or W <= 0, filter outside 0..5, W > 2^22 (offsets and cost sums
+ * inside a row are 32-bit), more than 2^31 - 1 rows in all. */
+int femasr_png_filter_rgb8(void *stream, const uint8_t *img, int B, int H, int W, int filter, uint8_t *out);
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
