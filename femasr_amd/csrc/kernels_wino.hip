@@ -24,8 +24,8 @@
 //             of component 32 + w/2: M += V_k[32 x 8] . U_k[8 x 32], 4 MFMAs per pair,
 //             U fragments stream from L2 through a register ring (1 KiB contiguous per wave load, issued one pair-group ahead)
 //   one barrier per step; every wave runs M then T (VALU work cannot hide behind a partner's MFMAs, see the main loop).
-// Epilogue: accumulators -> LDS per 32-column tile; thread = (Winograd tile, channel) applies A^T M A, bias, residuals,
-// stores, and accumulates the fused GroupNorm partial moments (fp64) per 16x16 sub-block in the order of orc_gn_coeffs mode 2.
+// Epilogue: accumulators -> LDS per 32-column tile; thread = (Winograd tile pair, channel) applies A^T M A, bias, residuals,
+// stores, and accumulates the fused GroupNorm partial moments (fp64) per 16x16 sub-block: described once in wino_common.h.
 #define FEMASR_WTT_BUF g_wi_ttbuf
 #include "wino_common.h"
 
@@ -38,36 +38,18 @@ namespace {
 // read, U pre-split at pack time, six v_mfma_f32_32x32x8_bf16_1k per (component, column tile) and step: fp32-grade, 4 % SLOWER per launch
 // (profiles/r05_wino_bf16m_ab.txt; DESIGN.md 5 "Round 5" 6.) - and round 6 removed it from the tree: git history has it.)
 template <int PRO, bool FAST, int NRES>
-__global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParams p)
+__global__ __launch_bounds__(WINO_NT, 2) void conv3x3_wino4_kernel(const WinoParams p)
 {
     constexpr bool HAS1 = NRES >= 1, HAS2 = NRES >= 2;      // residual operands of the epilogue (compile time: no selects per pixel)
-        extern __shared__ __attribute__((aligned(16))) float smem[];
+    extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Ps = smem;                        // [2][W4_PSZ]
     float *Vs = smem + 2 * W4_PSZ;           // [2][W4_VSZ]
     float *ABs = smem + W4_MAIN;             // [2 sub-blocks][a | b][Cin]
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    WTT_INIT
-    const int c31 = lane & 31, hh = lane >> 5;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB, mb = L / p.NB;
-    const int n0 = nb * 64;
-
-    // ---- the two sub-blocks (uniform)
-    int sn[2], sy0[2], sx0[2], sbi[2];
-    bool sval[2];
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-        const int sb = 2 * mb + z, per = p.sbY * p.sbX;
-        sval[z] = sb < p.nsb;
-        const int sbc = sval[z] ? sb : 0;
-        sn[z] = sbc / per;
-        sbi[z] = sbc - sn[z] * per;
-        const int by = sbi[z] / p.sbX, bx = sbi[z] - by * p.sbX;
-        sy0[z] = 16 * by;
-        sx0[z] = 16 * bx;
-    }
+    WinoFrame f(p);                          // block decode: the two sub-blocks (uniform)
+    const int t = f.t, lane = f.lane, wave = f.wave, c31 = f.c31, hh = f.hh, nb = f.nb, n0 = f.n0;
+    const auto &sn = f.sn, &sy0 = f.sy0, &sx0 = f.sx0;
+    const auto &sval = f.sval;
 
     // ---- staging units: float4 = (pixel of the 18x18 patch, channel quad t&1); unit u of the 2 x 648: u = t, t + 512, and 34 lanes
     // per wave of a third round.  The LDS slot of unit u is (u >> 1) * PS + 4 (u & 1) floats whatever its sub-block - the second
@@ -208,7 +190,7 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     const int aoff = c31 * 8 + hh * 4;
     auto pcomp = [&](int q) -> int { return q < 8 ? 4 * wave + (q >> 1) : 32 + (wave >> 1); };
     auto pntl = [&](int q) -> int { return q < 8 ? (q & 1) : (wave & 1); };
-    auto ldU = [&](int s, int q) -> u32x4_t {       // unconditional, like load_patch
+    auto ldU = [&](int s, int q) -> u32x4_t {       // unconditional, like load_patch (the x2 kernel has the same addressing with 25 components)
         const int sc = s < p.nsteps ? s : p.nsteps - 1;
         const int pr = (sc * 36 + pcomp(q)) * p.NT32 + 2 * nb + pntl(q);
         return __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, lw, pr << 10, 0);
@@ -252,7 +234,7 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
 #pragma unroll
     for (int q = 0; q < 3; ++q) ring[q] = ldU(0, q);
     if (PRO == FEMASR_PRO_GN_SILU) {     // GN table [sub-block][a | b][Cin]
-        for (int i = t; i < 2 * KINDS * p.Cin; i += W4_NT) {
+        for (int i = t; i < 2 * KINDS * p.Cin; i += WINO_NT) {
             const int z = i / (KINDS * p.Cin), r = i - z * KINDS * p.Cin, kind = r / p.Cin, c = r - kind * p.Cin;
             const float v = ((kind & 1) ? p.pro_b : p.pro_a)[(size_t)(z ? sn[1] : sn[0]) * p.Cin + c];
             ABs[i] = v;
@@ -317,19 +299,10 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
     WTT(1)
 
     // ---------------------------------------------------------------------------------------------------------------
-    // epilogue, one 32-column tile (round) at a time: accumulators -> Mx[component][tile pair][channel][2] (overlays the main-loop
-    // buffers; rows e, e + 1 of an accumulator tile are two horizontally adjacent Winograd tiles and sit in an aligned register
-    // pair: one ds_write_b64).  A thread = (tile pair pi = (sub-block, tile row, left / right half), channel c31) handles BOTH tiles
-    // at once: one ds_read_b64 per component, and every operation of the output transform, the bias / residual adds and the moment
-    // sums is a packed fp32 instruction over the pair (component-wise IEEE: the same values as two scalar sequences).  Outputs and
-    // residuals go through buffer instructions: descriptors in SGPRs (base = the image of sub-block 0), ONE 32-bit byte offset per
-    // lane, a uniform offset per pixel and tile of the pair; in a block whose 32 tiles lie wholly inside the image (FULL, the common
-    // case) nothing is masked; otherwise a pixel outside gets an offset beyond num_records (stores dropped, loads return 0).
-    // GroupNorm partial moments of what was stored (orc_gn_wino_partial): per (tile, channel) an fp32 sum and an fp32 fma chain of
-    // squares over the 16 pixels (row-major, a pixel outside adds +0), then fp64: the two tiles of the pair, the channels of the
-    // group (xor butterfly), the two pairs of the tile row, then the four tile rows (= waves) of the sub-block in order.
+    // epilogue (wino_common.h), one 32-column tile (round) at a time.  The border masks, `fetch` and `round` are written out here and in
+    // kernels_wino_up2.hip (same text but at6 / at5, three / two Mx bases, H, W / Ho, Wo): as shared functions they cost SGPR spills and a VGPR
     float *Mx = smem;
-    double *red = reinterpret_cast<double *>(smem + W4_MX);
+    double *red = reinterpret_cast<double *>(smem + wino_mx(6));
     const bool gnp = p.gn_part != nullptr;
     const int cg = p.Cout >> 5;                      // channels per GroupNorm group (>= 2: Cout % 64 == 0)
     const int gpt = 32 / (cg < 32 ? cg : 32);        // groups per 32-channel tile (<= 16)
@@ -352,10 +325,8 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         }
         ooff = (unsigned)((((ez ? sn[1] - sn[0] : 0) * p.H + oy) * p.W + ox) * p.Cout + n0 + c31) * 4u;      // (< 2^30: two images of < 2^27 elements)
     }
-    const size_t img0 = (size_t)sn[0] * p.H * p.W * p.Cout;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void *)(p.out + img0), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r1 = __builtin_amdgcn_make_buffer_rsrc((void *)((HAS1 ? p.res1 : p.out) + img0), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r2 = __builtin_amdgcn_make_buffer_rsrc((void *)((HAS2 ? p.res2 : p.out) + img0), 0, 0x7fffffff, 0x00020000);
+    f.template out_descriptors<NRES>(p);
+    const __amdgpu_buffer_rsrc_t rs_out = f.rs_out, rs_r1 = f.rs_r1, rs_r2 = f.rs_r2;
     // uniform byte offset of pixel k = 4a + b of tile e of the pair, round r: a * rs + (4e + b) * cs + 128 r.  The two strides are made
     // opaque once per round so that the 32 sums are formed where they are used (two scalar adds each) - hoisted out of the round loop
     // they do not fit the scalar registers and come back through v_readlane, which stalls every load / store on a scalar dependency
@@ -465,10 +436,7 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
             if (pntl(q) == R) {
-                char *dst = q < 8 ? wb0 + (q >> 1) * 4096 : wb1;
-#pragma unroll
-                for (int e = 0; e < 16; e += 2)      // pair row ((e & 3) + 8 (e >> 2) + 4 hh) / 2, 256 bytes each
-                    *reinterpret_cast<tf2 *>(dst + (((e & 3) >> 1) + 4 * (e >> 2)) * 256) = tf2{acc[q][e], acc[q][e + 1]};
+                f.store_acc_tile(q < 8 ? wb0 + (q >> 1) * 4096 : wb1, acc[q]);
             }
         }
     };
@@ -480,48 +448,9 @@ __global__ __launch_bounds__(W4_NT, 2) void conv3x3_wino4_kernel(const WinoParam
         if (full) round(std::true_type{}, r); else round(std::false_type{}, r);
         __syncthreads();
         WTT(5 + 4 * r)
-        if (gnp && t < 2 * gpt) {
-            const int z = t / gpt, gl = t - z * gpt;
-            if (z ? sval[1] : sval[0]) {
-                double S = red[((size_t)(4 * z) * 16 + gl) * 2], SS = red[((size_t)(4 * z) * 16 + gl) * 2 + 1];
-#pragma unroll
-                for (int w = 1; w < 4; ++w) {
-                    S = S + red[((size_t)(4 * z + w) * 16 + gl) * 2];
-                    SS = SS + red[((size_t)(4 * z + w) * 16 + gl) * 2 + 1];
-                }
-                const int g = (n0 + 32 * r) / cg + gl;
-                double *dst = p.gn_part + (((size_t)(z ? sn[1] : sn[0]) * p.sbY * p.sbX + (z ? sbi[1] : sbi[0])) * 32 + g) * 2;
-                dst[0] = S;
-                dst[1] = SS;
-            }
-        }
+        f.gn_reduce(p, red, cg, gpt, r);
     }
     WTT_END
-}
-
-// 3x3 OIHW -> out[step = ci/8][component 6 i + j][32-column tile][lane][e]: column o = 32 tile + lane%32,
-// ci = 8 step + 2 e + lane/32 (the B fragments of the four k-pairs of a step: one 16-byte load per lane, 1 KiB per wave)
-__global__ void repack_wino_kernel(const float *__restrict__ in, int O, int I, float *__restrict__ out, size_t total)
-{
-    const int NT32 = (O + 31) / 32;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int e = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
-        size_t rest = idx >> 8;
-        const int ntile = (int)(rest % NT32);
-        rest /= NT32;
-        const int comp = (int)(rest % 36), step = (int)(rest / 36);
-        const int ci = 8 * step + 2 * e + (lane >> 5), o = ntile * 32 + (lane & 31);
-        float v = 0.f;
-        if (ci < I && o < O) {
-            const int i = comp / 6, j = comp - 6 * i;
-            const float *gw = in + ((size_t)o * I + ci) * 9;
-            float ur[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) ur[x] = wino_g6(i, gw[x], gw[3 + x], gw[6 + x]);
-            v = wino_g6(j, ur[0], ur[1], ur[2]);
-        }
-        out[idx] = v;
-    }
 }
 
 struct WVariant {
@@ -540,17 +469,9 @@ constexpr int kNumW = sizeof(g_wv) / sizeof(g_wv[0]);
 
 }  // namespace
 
-// Element limits of the Winograd-form kernels (32-bit byte offsets: 2^31 elements per tensor, 2^27 per image).  A handle may LOWER them
-// for its planner (femasr_debug_set_wino_limits, include/femasr_hip_debug.h: tests of both sides of the limit at sizes they can allocate).
 bool femasr_conv_wino_shape_ok_lim(const femasr_conv_args *a, int log2_total, int log2_image)
 {
-    const size_t tot = (size_t)1 << log2_total, img = (size_t)1 << log2_image;
-    return a->ksz == 3 && a->stride == 1 && a->pad == 1 && !a->up2 && a->act == FEMASR_ACT_NONE && (a->Cin % BK) == 0 && a->Cin <= W4_MAX_CIN &&
-           (a->Cout % 64) == 0 && (a->prologue == FEMASR_PRO_NONE || a->prologue == FEMASR_PRO_GN_SILU) &&
-           (size_t)a->B * a->H * a->W * a->Cin < tot && (size_t)a->B * a->H * a->W * a->Cout < tot &&
-           (size_t)a->H * a->W * a->Cin < img &&          // two images within the 2 GiB range of the input descriptor
-           (size_t)a->H * a->W * a->Cout < img &&         // ... and of the output / residual descriptors
-           (size_t)36 * a->Cin * a->Cout < ((size_t)1 << 29);
+    return wino_shape_ok(a, 6, 1, log2_total, log2_image) && !a->up2 && (a->prologue == FEMASR_PRO_NONE || a->prologue == FEMASR_PRO_GN_SILU);
 }
 bool femasr_conv_wino_shape_ok(const femasr_conv_args *a) { return femasr_conv_wino_shape_ok_lim(a, FEMASR_WINO_LOG2_TOTAL, FEMASR_WINO_LOG2_IMAGE); }
 int femasr_conv_wino_variant_count() { return kNumW; }
@@ -569,26 +490,15 @@ int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *varia
     FEMASR_REQUIRE(a->Ho == a->H && a->Wo == a->W, "conv_wino: Ho/Wo mismatch");
     const bool gn = a->prologue == FEMASR_PRO_GN_SILU;
     if (gn) FEMASR_REQUIRE(a->pro_a && a->pro_b, "conv_wino: GN prologue needs a,b");
-    FEMASR_REQUIRE(!a->gn_part || femasr_gn_fusable(a->Cout), "conv_wino: gn_part needs 32 | Cout and Cout/32 a power of two <= 32");
-    WinoParams p{};
-    p.in = a->in; p.u = (const float *)a->w_wino; p.bias = a->bias; p.pro_a = a->pro_a; p.pro_b = a->pro_b;
-    p.res1 = a->res1; p.res2 = a->res2; p.out = a->out; p.gn_part = a->gn_part;
-    p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout;
-    p.sbX = (a->W + 15) / 16;
-    p.sbY = (a->H + 15) / 16;
-    p.nsb = a->B * p.sbX * p.sbY;
-    p.MB = (p.nsb + 1) / 2;
-    p.NB = a->Cout / 64;
-    p.nsteps = a->Cin / 8;
-    p.NT32 = a->Cout / 32;
-    FEMASR_REQUIRE(a->res1 || !a->res2, "conv_wino: res2 without res1");
     FEMASR_REQUIRE(!a->in_add, "conv_wino: in_add is only taken by the x2 form");
+    WinoParams p{};
+    FEMASR_CHECK(wino_params(a, "conv_wino", p));
     const int vi = femasr_conv_wino_pick_variant(a);
     WVariant &v = g_wv[vi];
     // the attribute is only a cap: set once per device to the kernel's maximum; the launch asks for what this shape uses
-    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, wino_lds_bytes(W4_MAX_CIN, true)));
-    const size_t lds = wino_lds_bytes(a->Cin, gn);
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(W4_NT), lds, s, p);
+    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, wino_lds_bytes(6, W4_MAIN, WINO_MAX_CIN)));
+    const size_t lds = wino_lds_bytes(6, W4_MAIN, gn ? a->Cin : 0);
+    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(WINO_NT), lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     if (variant_out) *variant_out = vi;
     // ALGORITHMIC flops (the definition's 9 taps per output pixel, like every other conv launcher); the kernel issues 36/144 of them
@@ -599,23 +509,17 @@ int femasr_conv_wino_launch(hipStream_t s, const femasr_conv_args *a, int *varia
 extern "C" {
 
 #ifdef FEMASR_WINO_TT
-int femasr_debug_wino_ttbuf(unsigned long long *dev_buf)      // [blocks][2][64] on the device, zero-filled by the caller
+int femasr_debug_wino_ttbuf(unsigned long long *dev_buf)      // [blocks][2][128] on the device, zero-filled by the caller
 {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_wi_ttbuf), &dev_buf, sizeof(dev_buf));
 }
 #endif
 
-size_t femasr_wino_weight_floats(int O, int I) { return (I % 32) == 0 ? (size_t)(I / 8) * 36 * ((O + 31) / 32) * 256 : 0; }
+size_t femasr_wino_weight_floats(int O, int I) { return wino_weight_floats(6, O, I); }
 
 int femasr_repack_oihw_wino(void *stream, const float *in, int O, int I, float *out)
 {
-    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 32) == 0, "repack_wino: needs a 3x3 OIHW weight with I %% 32 == 0");
-    const size_t total = femasr_wino_weight_floats(O, I);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(repack_wino_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, O, I, out, total);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    return FEMASR_OK;
+    return wino_repack<6, wino_g6>(stream, in, O, I, out, "repack_wino");
 }
 
 }  // extern "C"

@@ -16,102 +16,30 @@
 //
 // Structure = kernels_wino.hip (read its header first): block = 8 waves, two 16x16-pixel OUTPUT sub-blocks (= 2 x 16 tiles =
 // one 32-row MFMA tile) x 64 output channels, K in steps of 8 input channels, every wave M phase then T phase, one barrier
-// per step.  What differs:
+// per step; the block decode and the shared parts of the epilogue are WinoFrame (wino_common.h).  What differs:
 //   staging   the 10x10 low-resolution patch of a sub-block (8x8 + halo), plain copy (these convs have no GN prologue)
 //   T phase   thread = (tile, channel, half): 12 LDS reads -> 8 of the 16 DISTINCT transformed values V[4][4] (components P and
 //             Q share v3): V[16][32 tiles][8 channels]
 //   M phase   50 (component, 32-column tile) pairs: wave w owns column tile w&1 of components w/2 + 4q, q = 0..5 (waves 0, 1
 //             also q = 6): 13 / 13 / 12 / 12 pairs per SIMD
-//   epilogue  Mx[25][32][32] per column tile, thread = (tile, channel) applies the 5 -> 4 output transform twice
-#include "conv_common.h"
-#include <stdlib.h>
-#include <type_traits>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float tf2 __attribute__((ext_vector_type(2)));
-
-#ifdef FEMASR_WINO_TT      // tools/build_debug.sh tt: cycle stamps of waves 0 and 7 of every block in a global buffer, see kernels_wino.hip
-// (same slots: 63 start, 0 prologue done, 16 + s step s done, 1 main loop done, 2..5 + 4r epilogue round r, 10 end)
-__device__ unsigned long long *g_wu_ttbuf;
-#define WUTT(slot) { if (lane == 0 && (wave == 0 || wave == 7)) g_wu_ttbuf[((size_t)blockIdx.x * 2 + (wave == 7 ? 1 : 0)) * 64 + (slot)] = __builtin_readcyclecounter(); }
-#define WUTTR(slot) { if (lane == 0 && (wave == 0 || wave == 7)) g_wu_ttbuf[((size_t)blockIdx.x * 2 + (wave == 7 ? 1 : 0)) * 64 + (slot)] = wall_clock64(); }
-#define WUTT_INIT { WUTTR(62) WUTT(63) }
-#define WUTT_END { WUTT(10) WUTTR(11) }
-#else
-#define WUTT(slot) {}
-#define WUTT_INIT
-#define WUTT_END {}
-#endif
-
-// (Measured in round 4 and removed: the transform's patch reads at the start of the M phase, or the whole transform inside the M phase -
-// +-1 %, profiles/r04_wino_variants.txt; the nt cache-policy bit on the streaming accesses - slower or +-2 %, profiles/r04_i_wino_nt.txt.
-// Kept: the two-set patch prefetch of kernels_wino.hip.)
+//   epilogue  (wino_common.h) Mx[25][32][32] per column tile, the 5 -> 4 output transform (at5) twice
+#define FEMASR_WTT_BUF g_wu_ttbuf
+#include "wino_common.h"
 
 namespace {
 
-struct WinoUpParams {
-    const float *in, *in2, *u, *bias, *res1, *res2;      // in2: optional second input, added to `in` while staging (femasr_conv_args.in_add)
-    float *out;
-    double *gn_part;
-    int B, H, W, Cin, Cout, Ho, Wo;     // H, W: low-resolution input; Ho = 2H, Wo = 2W
-    int sbX, sbY, nsb;                  // 16x16-pixel output sub-blocks per row / per column / in the batch
-    int MB, NB, nsteps, NT32;
-};
-
-constexpr int WU_NT = 512;
-constexpr int WU_PS = 12;                         // floats per patch pixel: 8 channels + 4
-constexpr int WU_PW = 10;
-constexpr int WU_PPIX = WU_PW * WU_PW;            // 100
-constexpr int WU_PSZ = 2 * WU_PPIX * WU_PS;       // floats per patch buffer (two sub-blocks): 2400
-constexpr int WU_VSZ = 16 * 32 * 8;               // floats per V buffer: 4096
-constexpr int WU_MAIN = 2 * WU_PSZ + 2 * WU_VSZ;
-constexpr int WU_MX = 25 * 32 * 32;               // epilogue: one 32-column tile of all components
-constexpr int WU_RED = 8 * 2 * 16 * 2 * 2;        // floats: [8 waves][2 sub-blocks][<= 16 groups][2] doubles
-constexpr int WU_UNITS = 2 * WU_PPIX * 2;         // float4 staging units per step: 400
-
-inline size_t wino_up_lds_bytes() { return (size_t)((WU_MX + WU_RED) > WU_MAIN ? (WU_MX + WU_RED) : WU_MAIN) * sizeof(float); }
-
-// output rows of the 5 -> 4 transform (see the header), on PAIRS (two horizontally adjacent tiles): v_pk_add_f32 / v_pk_fma_f32
-// are IEEE per component
-__device__ __forceinline__ void at5(tf2 m0, tf2 m1, tf2 mP, tf2 mQ, tf2 m5, tf2 &y0, tf2 &y1, tf2 &y2, tf2 &y3)
-{
-    y0 = (m0 + m1) + mP;
-    y1 = __builtin_elementwise_fma(tf2{2.0f, 2.0f}, mQ, m1);
-    y2 = __builtin_elementwise_fma(tf2{4.0f, 4.0f}, mP, m1);
-    y3 = __builtin_elementwise_fma(tf2{8.0f, 8.0f}, mQ, m1) + m5;
-}
-
 template <int NRES, bool ADD>
-__global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUpParams p)
+__global__ __launch_bounds__(WINO_NT, 2) void conv3x3_wino_up2_kernel(const WinoParams p)
 {
     constexpr bool HAS1 = NRES >= 1, HAS2 = NRES >= 2;      // residual operands of the epilogue (compile time; the network's x2 convs have none)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Ps = smem;                        // [2][WU_PSZ]
     float *Vs = smem + 2 * WU_PSZ;           // [2][WU_VSZ]
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    WUTT_INIT
-    const int c31 = lane & 31, hh = lane >> 5;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB, mb = L / p.NB;
-    const int n0 = nb * 64;
-
-    // ---- the two output sub-blocks (uniform)
-    int sn[2], sy0[2], sx0[2], sbi[2];
-    bool sval[2];
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-        const int sb = 2 * mb + z, per = p.sbY * p.sbX;
-        sval[z] = sb < p.nsb;
-        const int sbc = sval[z] ? sb : 0;
-        sn[z] = sbc / per;
-        sbi[z] = sbc - sn[z] * per;
-        const int by = sbi[z] / p.sbX, bx = sbi[z] - by * p.sbX;
-        sy0[z] = 16 * by;
-        sx0[z] = 16 * bx;
-    }
+    WinoFrame f(p);                          // block decode: the two output sub-blocks (uniform)
+    const int t = f.t, lane = f.lane, wave = f.wave, c31 = f.c31, hh = f.hh, nb = f.nb, n0 = f.n0;
+    const auto &sn = f.sn, &sy0 = f.sy0, &sx0 = f.sx0;
+    const auto &sval = f.sval;
 
     // ---- staging unit of this thread (threads 0..399): (sub-block z, pixel of its 10x10 low-resolution patch, channel quad)
     const __amdgpu_buffer_rsrc_t rsrc_in = __builtin_amdgcn_make_buffer_rsrc((void *)(p.in + (size_t)sn[0] * p.H * p.W * p.Cin), 0, 0x7fffffff, 0x00020000);
@@ -200,7 +128,7 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         const int c = pcomp(q), i = c / 5, j = c - 5 * i;
         return ((i > 2 ? i - 1 : i) << 2) + (j > 2 ? j - 1 : j);
     };
-    auto ldU = [&](int s, int q) -> f32x4_t {  // unconditional, like load_patch
+    auto ldU = [&](int s, int q) -> f32x4_t {  // unconditional, like load_patch (the addressing of kernels_wino.hip with 25 components)
         const int sc = s < p.nsteps ? s : p.nsteps - 1;
         return __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, lw, (((sc * 25 + pcomp(q)) * p.NT32 + 2 * nb + wnt) << 10), 0));
     };
@@ -252,7 +180,7 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
     transform_write(0);
     issue_early(0);
     __syncthreads();
-    WUTT(0)
+    WTT(0)
 
     // ---- main loop.  Per step: M(s); transform of step s+1 (its patch was staged during step s-1); stage step s+2.
     // (Measured and dropped: 32-channel blocks with half the accumulators, <= 128 VGPRs and a 16-column epilogue exchange, so that
@@ -272,22 +200,19 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         if (PAR) store_patch_from(rq, PAR); else store_patch_from(rp, PAR);
         issue_early(s + 1);
         __syncthreads();
-        if (s < 40) WUTT(16 + s)
+        if (s < 40) WTT(16 + s)
     };
     for (int s = 0; s < p.nsteps; s += 2) {       // (nsteps = Cin / 8 is a multiple of 4)
         step(s, std::integral_constant<int, 0>{});
         step(s + 1, std::integral_constant<int, 1>{});
     }
-    WUTT(1)
+    WTT(1)
 
     // ---------------------------------------------------------------------------------------------------------------
-    // epilogue = the F(4x4,3x3) kernel's (kernels_wino.hip), with 25 components and the 5 -> 4 transform: one 32-column tile
-    // (round) at a time, accumulators -> Mx[component][tile pair][channel][2] (rows e, e + 1 of an accumulator tile = two
-    // horizontally adjacent tiles = one aligned register pair = one ds_write_b64); a thread = (tile pair, channel) runs both tiles
-    // as packed fp32; outputs / residuals through buffer instructions with one per-lane offset; nothing is masked in a block
-    // whose 32 tiles lie inside the image (FULL); GroupNorm partial moments in the order of orc_gn_wino_partial.
+    // epilogue (wino_common.h) with 25 components and the 5 -> 4 transform.  The border masks, `fetch` and `round` are the text of
+    // kernels_wino.hip (its comments apply) with at5, two Mx bases and Ho, Wo: as shared functions they cost SGPR spills and VGPRs
     float *Mx = smem;
-    double *red = reinterpret_cast<double *>(smem + WU_MX);
+    double *red = reinterpret_cast<double *>(smem + wino_mx(5));
     const bool gnp = p.gn_part != nullptr;
     const int cg = p.Cout >> 5;                      // channels per GroupNorm group (>= 2: Cout % 64 == 0)
     const int gpt = 32 / (cg < 32 ? cg : 32);        // groups per 32-channel tile (<= 16)
@@ -310,10 +235,8 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         }
         ooff = (unsigned)((((ez ? sn[1] - sn[0] : 0) * p.Ho + oy) * p.Wo + ox) * p.Cout + n0 + c31) * 4u;      // (< 2^30: two images of < 2^27 elements)
     }
-    const size_t img0 = (size_t)sn[0] * p.Ho * p.Wo * p.Cout;
-    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc((void *)(p.out + img0), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r1 = __builtin_amdgcn_make_buffer_rsrc((void *)((HAS1 ? p.res1 : p.out) + img0), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r2 = __builtin_amdgcn_make_buffer_rsrc((void *)((HAS2 ? p.res2 : p.out) + img0), 0, 0x7fffffff, 0x00020000);
+    f.template out_descriptors<NRES>(p);
+    const __amdgpu_buffer_rsrc_t rs_out = f.rs_out, rs_r1 = f.rs_r1, rs_r2 = f.rs_r2;
     // uniform byte offset of pixel k = 4a + b of tile e, round r; the two strides are made opaque once per round (kernels_wino.hip)
     int cs_u = 0, rs_u = 0;
     auto soff = [&](int k, int e, int r) -> int { return (k >> 2) * rs_u + (4 * e + (k & 3)) * cs_u + 128 * r; };
@@ -343,7 +266,7 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
         }
         const float bv = p.bias[n0 + 32 * r + c31];
         __syncthreads();
-        WUTT(3 + 4 * r)
+        WTT(3 + 4 * r)
         {
             // component stride: 16 tile pairs x 32 channels = 4 KiB; two bases keep every read inside the 64-KiB offset field
             int so1 = (16 * 512 + pi * 32 + c31) * 8;
@@ -400,7 +323,7 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
                 }
             }
         }
-        WUTT(4 + 4 * r)
+        WTT(4 + 4 * r)
     };
     // (one per-lane base, pinned as an integer offset: a wave's pairs are the components wave / 2 + 4 q; everything else is an
     // immediate offset)
@@ -410,79 +333,22 @@ __global__ __launch_bounds__(WU_NT, 2) void conv3x3_wino_up2_kernel(const WinoUp
     auto write_acc = [&]() {
 #pragma unroll
         for (int q = 0; q < 7; ++q) {
-            if (q < 6 || has6) {
-                char *dst = wb0 + q * 4 * 4096;
-#pragma unroll
-                for (int e = 0; e < 16; e += 2)      // pair row ((e & 3) + 8 (e >> 2) + 4 hh) / 2, 256 bytes each
-                    *reinterpret_cast<tf2 *>(dst + (((e & 3) >> 1) + 4 * (e >> 2)) * 256) = tf2{acc[q][e], acc[q][e + 1]};
-            }
+            if (q < 6 || has6) f.store_acc_tile(wb0 + q * 4 * 4096, acc[q]);
         }
     };
 #pragma unroll 1
     for (int r = 0; r < 2; ++r) {
         if (wnt == r) write_acc();
-        WUTT(2 + 4 * r)
+        WTT(2 + 4 * r)
         if (full) round(std::true_type{}, r); else round(std::false_type{}, r);
         __syncthreads();
-        WUTT(5 + 4 * r)
-        if (gnp && t < 2 * gpt) {
-            const int z = t / gpt, gl = t - z * gpt;
-            if (z ? sval[1] : sval[0]) {
-                double S = red[((size_t)(4 * z) * 16 + gl) * 2], SS = red[((size_t)(4 * z) * 16 + gl) * 2 + 1];
-#pragma unroll
-                for (int w = 1; w < 4; ++w) {
-                    S = S + red[((size_t)(4 * z + w) * 16 + gl) * 2];
-                    SS = SS + red[((size_t)(4 * z + w) * 16 + gl) * 2 + 1];
-                }
-                const int g = (n0 + 32 * r) / cg + gl;
-                double *dst = p.gn_part + (((size_t)(z ? sn[1] : sn[0]) * p.sbY * p.sbX + (z ? sbi[1] : sbi[0])) * 32 + g) * 2;
-                dst[0] = S;
-                dst[1] = SS;
-            }
-        }
+        WTT(5 + 4 * r)
+        f.gn_reduce(p, red, cg, gpt, r);
     }
-    WUTT_END
+    WTT_END
 }
 
-// the five 1-D filters of the form (header): rows (over ky) then columns (over kx)
-__device__ __forceinline__ float e5(int r, float g0, float g1, float g2)
-{
-    const float c3 = -1.0f / 3.0f, c12 = 1.0f / 12.0f, c6 = 1.0f / 6.0f;
-    switch (r) {
-    case 0: return g0 * 0.25f;
-    case 1: return ((g0 + g1) + g2) * c3;
-    case 2: return __builtin_fmaf(4.0f, g2, __builtin_fmaf(4.0f, g1, g0)) * c12;
-    case 3: return __builtin_fmaf(4.0f, g2, g0 + g1) * c6;
-    default: return g2;
-    }
-}
-
-// 3x3 OIHW -> out[step = ci/8][component 5 i + j][32-column tile][lane][e]: column o = 32 tile + lane%32,
-// ci = 8 step + 2 e + lane/32 (the B fragments of the four k-pairs of a step: one 16-byte load per lane, 1 KiB per wave)
-__global__ void repack_wino_up2_kernel(const float *__restrict__ in, int O, int I, float *__restrict__ out, size_t total)
-{
-    const int NT32 = (O + 31) / 32;
-    for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int e = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
-        size_t rest = idx >> 8;
-        const int ntile = (int)(rest % NT32);
-        rest /= NT32;
-        const int comp = (int)(rest % 25), step = (int)(rest / 25);
-        const int ci = 8 * step + 2 * e + (lane >> 5), o = ntile * 32 + (lane & 31);
-        float v = 0.f;
-        if (ci < I && o < O) {
-            const int i = comp / 5, j = comp - 5 * i;
-            const float *gw = in + ((size_t)o * I + ci) * 9;
-            float ur[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) ur[x] = e5(i, gw[x], gw[3 + x], gw[6 + x]);
-            v = e5(j, ur[0], ur[1], ur[2]);
-        }
-        out[idx] = v;
-    }
-}
-
-typedef void (*wu_kern_t)(const WinoUpParams);
+typedef void (*wu_kern_t)(const WinoParams);
 wu_kern_t g_wu_kern[6] = {conv3x3_wino_up2_kernel<0, false>, conv3x3_wino_up2_kernel<1, false>, conv3x3_wino_up2_kernel<2, false>,      // [2 * ... ]: by residual
                           conv3x3_wino_up2_kernel<0, true>, conv3x3_wino_up2_kernel<1, true>, conv3x3_wino_up2_kernel<2, true>};          // operands, then + second input
 unsigned long long g_attr_devs[6] = {0, 0, 0, 0, 0, 0};
@@ -491,13 +357,7 @@ unsigned long long g_attr_devs[6] = {0, 0, 0, 0, 0, 0};
 
 bool femasr_conv_wino_up2_shape_ok_lim(const femasr_conv_args *a, int log2_total, int log2_image)
 {
-    const size_t tot = (size_t)1 << log2_total, img = (size_t)1 << log2_image;
-    return a->ksz == 3 && a->stride == 1 && a->pad == 1 && a->up2 && a->act == FEMASR_ACT_NONE && a->prologue == FEMASR_PRO_NONE &&
-           (a->Cin % BK) == 0 && a->Cin <= 1024 && (a->Cout % 64) == 0 &&
-           (size_t)a->B * a->H * a->W * a->Cin < tot && (size_t)a->B * 4 * a->H * a->W * a->Cout < tot &&
-           (size_t)a->H * a->W * a->Cin < img &&          // two images within the 2 GiB range of the input descriptor
-           (size_t)4 * a->H * a->W * a->Cout < img &&     // ... and of the output descriptor
-           (size_t)25 * a->Cin * a->Cout < ((size_t)1 << 29);
+    return wino_shape_ok(a, 5, 2, log2_total, log2_image) && a->up2 && a->prologue == FEMASR_PRO_NONE;
 }
 bool femasr_conv_wino_up2_shape_ok(const femasr_conv_args *a) { return femasr_conv_wino_up2_shape_ok_lim(a, FEMASR_WINO_LOG2_TOTAL, FEMASR_WINO_LOG2_IMAGE); }
 const char *femasr_conv_wino_up2_variant_name() { return "conv3x3_wino_up2<2x16x16px x64,waves=8>"; }
@@ -506,23 +366,12 @@ int femasr_conv_wino_up2_launch(hipStream_t s, const femasr_conv_args *a, double
 {
     FEMASR_REQUIRE(a && a->in && a->w_wino && a->bias && a->out && femasr_conv_wino_up2_shape_ok(a), "conv_wino_up2: bad arguments / shape");
     FEMASR_REQUIRE(a->Ho == 2 * a->H && a->Wo == 2 * a->W, "conv_wino_up2: Ho/Wo mismatch");
-    FEMASR_REQUIRE(!a->gn_part || femasr_gn_fusable(a->Cout), "conv_wino_up2: gn_part needs 32 | Cout and Cout/32 a power of two <= 32");
-    WinoUpParams p{};
-    p.in = a->in; p.in2 = a->in_add; p.u = (const float *)a->w_wino; p.bias = a->bias;
-    p.res1 = a->res1; p.res2 = a->res2; p.out = a->out; p.gn_part = a->gn_part;
-    p.B = a->B; p.H = a->H; p.W = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.Ho = a->Ho; p.Wo = a->Wo;
-    p.sbX = (p.Wo + 15) / 16;
-    p.sbY = (p.Ho + 15) / 16;
-    p.nsb = a->B * p.sbX * p.sbY;
-    p.MB = (p.nsb + 1) / 2;
-    p.NB = a->Cout / 64;
-    p.nsteps = a->Cin / 8;
-    p.NT32 = a->Cout / 32;
-    FEMASR_REQUIRE(a->res1 || !a->res2, "conv_wino_up2: res2 without res1");
+    WinoParams p{};
+    FEMASR_CHECK(wino_params(a, "conv_wino_up2", p));
     const int nres = (a->res1 ? (a->res2 ? 2 : 1) : 0) + (a->in_add ? 3 : 0);      // (index into the instantiation table)
-    const size_t lds = wino_up_lds_bytes();
+    const size_t lds = wino_lds_bytes(5, WU_MAIN, 0);
     FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)g_wu_kern[nres], &g_attr_devs[nres], lds));
-    hipLaunchKernelGGL(g_wu_kern[nres], dim3((unsigned)(p.MB * p.NB)), dim3(WU_NT), lds, s, p);
+    hipLaunchKernelGGL(g_wu_kern[nres], dim3((unsigned)(p.MB * p.NB)), dim3(WINO_NT), lds, s, p);
     FEMASR_CHECK_HIP(hipGetLastError());
     // ALGORITHMIC flops (the definition's 9 taps per output pixel, like every other conv launcher); the kernel issues 25/144 of them
     if (flops_out) *flops_out = 2.0 * (double)a->B * a->Ho * a->Wo * 9.0 * (double)a->Cin * (double)a->Cout;
@@ -538,17 +387,11 @@ int femasr_debug_wino_up2_ttbuf(unsigned long long *dev_buf)
 }
 #endif
 
-size_t femasr_wino_up2_weight_floats(int O, int I) { return (I % 32) == 0 ? (size_t)(I / 8) * 25 * ((O + 31) / 32) * 256 : 0; }
+size_t femasr_wino_up2_weight_floats(int O, int I) { return wino_weight_floats(5, O, I); }
 
 int femasr_repack_oihw_wino_up2(void *stream, const float *in, int O, int I, float *out)
 {
-    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 32) == 0, "repack_wino_up2: needs a 3x3 OIHW weight with I %% 32 == 0");
-    const size_t total = femasr_wino_up2_weight_floats(O, I);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(repack_wino_up2_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, O, I, out, total);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    return FEMASR_OK;
+    return wino_repack<5, e5>(stream, in, O, I, out, "repack_wino_up2");
 }
 
 }  // extern "C"

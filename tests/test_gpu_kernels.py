@@ -418,6 +418,32 @@ def test_conv_up2_winograd_bit_exact(cuda_device, cin, cout, shape, nres, part):
         _same(bb, b_ref, 'fused gn b (up2 winograd)')
 
 
+@pytest.mark.parametrize('in_add', [False, True])
+@pytest.mark.parametrize('nres', [0, 1, 2])
+def test_conv_up2_winograd_border_block_every_instantiation(cuda_device, nres, in_add):
+    """Each of the six instantiations of the x2 Winograd-type kernel (residual operands x second input) on a border block with
+    GroupNorm partials: 2 x 5 x 7 -> 10 x 14 outputs is one 16x16 sub-block per image, so the two sub-blocks of the only block lie in
+    different images and neither is full.  Reference: the oracle's Winograd restatement on x + in_add; image and GroupNorm
+    coefficients bit for bit."""
+    import gpu_utils as G
+    cin, cout, (b, h, w) = 64, 64, (2, 5, 7)
+    x = synth.uniform(29, 'wbx', (b, h, w, cin), -2.0, 2.0)
+    sk = synth.uniform(29, 'wbs', (b, h, w, cin), -1.0, 1.0) if in_add else None
+    wt = synth.uniform(29, 'wbw', (3, 3, cin, cout), -0.1, 0.1)
+    bias = synth.uniform(29, 'wbb', (cout,), -0.5, 0.5)
+    res = [synth.uniform(29, f'wbr{k}', (b, 2 * h, 2 * w, cout), -1, 1) for k in range(nres)]
+    r1, r2 = (res + [None, None])[:2]
+    ref = orc.conv2d((x + sk).astype(np.float32) if in_add else x, wt, bias, 3, 1, 1, True, res1=r1, res2=r2, wino=True)
+    y, part = G.conv2d(x, wt, bias, 3, 1, 1, True, res1=r1, res2=r2, wino=True, gn_part=True, in_add=sk)
+    _same(y, ref, 'up2 conv (Winograd-type form), border block')
+    gamma = synth.uniform(29, 'wbg', (cout,), 0.5, 1.5)
+    beta = synth.uniform(29, 'wbbe', (cout,), -0.5, 0.5)
+    a_ref, b_ref = orc.gn_coeffs(ref, gamma, beta, phases=2)
+    a, bb = G.gn_coeffs_from_partials(part, 2 * h, 2 * w, cout, gamma, beta)
+    _same(a, a_ref, 'fused gn a (up2 winograd, border block)')
+    _same(bb, b_ref, 'fused gn b (up2 winograd, border block)')
+
+
 @pytest.mark.parametrize('cin,cout,shape,nres', [(64, 128, (2, 16, 32), 1), (128, 64, (1, 13, 21), 2), (256, 256, (1, 20, 9), 0)])
 def test_conv_winograd_fast_act_close(cuda_device, cin, cout, shape, nres):
     """The model's default for the convs behind the codebook lookup: Winograd form with the SiLU of the GroupNorm prologue on the

@@ -37,7 +37,7 @@ def tt_report(T, nsteps, floor=4608):
         print('    %-22s %8.2f us  %5.1f %%   (min %.2f max %.2f)' % (n, us(v.mean()), 100 * v.mean() / cyc.mean(), us(v.min()), us(v.max())))
     print('    per step: mean %.3f us (%.0f cycles; first %.0f, median step %.0f, last %.0f; MFMA floor %d)'
           % (us(steps.mean()), steps.mean(), steps[:, 0].mean(), np.median(steps.mean(axis=0)), steps[:, -1].mean(), floor))
-    if T.shape[2] > 64:        # inside the steps: M phase issued / T phase done / barrier passed
+    if w0[:, 64].any():        # inside the steps (stamped by the F(4x4) kernel only): M phase issued / T phase done / barrier passed
         n2 = min(ns, 24)
         m_end, t_end = w0[:, 64:64 + 2 * n2:2], w0[:, 65:65 + 2 * n2:2]
         start = np.concatenate([w0[:, 0:1], w0[:, 16:16 + n2 - 1]], axis=1)
@@ -130,7 +130,7 @@ def main():
     if tt:
         nsb = b * ((ho + 15) // 16) * ((wo + 15) // 16)
         nblk = nsb * (cout // 128) if c128 else ((nsb + 1) // 2) * (cout // 64)
-        TTS = 64 if a_.up2 else 128
+        TTS = 128       # slots per stamped wave (WTT, wino_common.h)
         ttbuf = torch.zeros(nblk * 2 * TTS, dtype=torch.int64, device=dev)
         tt_fn.argtypes = [ctypes.c_void_p]
         assert tt_fn(ttbuf.data_ptr()) == 0
