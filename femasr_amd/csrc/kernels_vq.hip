@@ -352,6 +352,21 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void vq_candidates_kernel(const Vq
     }
     __syncthreads();
     if (!FUSED) {
+        // The unit entry's lists are its RESULT: the reservation order of the atomics above differs from run to run, and a slot nobody
+        // reserved holds whatever LDS held.  Written out: the row's codes ascending, zeros behind them (every slot of an overflowed row).
+        if (t < VQ_R) {
+            unsigned short *c = s_code + t * VQ_CMAX;
+            const unsigned n0 = s_cnt[t];
+            const int n = n0 > (unsigned)VQ_CMAX ? 0 : (int)n0;
+            for (int i = 1; i < n; ++i) {
+                const unsigned short v = c[i];
+                int j = i - 1;
+                for (; j >= 0 && c[j] > v; --j) c[j + 1] = c[j];
+                c[j + 1] = v;
+            }
+            for (int i = n; i < VQ_CMAX; ++i) c[i] = 0;
+        }
+        __syncthreads();
         // lists -> global: (M, VQ_CMAX) uint16, 8 B per thread
         for (int i = t; i < VQ_R * (VQ_CMAX / 4); i += NW * 64) {
             const int r = i / (VQ_CMAX / 4), q = i % (VQ_CMAX / 4);

@@ -281,7 +281,10 @@ int femasr_vq_prepare(void *stream, const float *cb, const float *ee, int n_e, i
 size_t femasr_vq_scratch_bytes(int64_t M, int n_e);
 int femasr_vq_twopass(void *stream, const float *z, int64_t M, int D, const float *cb, const void *aux, const float *ee,
                       int n_e, int64_t *idx, float *zq, void *scratch);
-/* Pass 1 alone: cand (M,32) uint16 candidate codes, cnt (M) uint16 count (0xFFFF = every code). */
+/* Pass 1 alone: cand (M,32) uint16 candidate codes, cnt (M) uint16 count (0xFFFF = every code).  Every one of the M * 32 slots is
+ * written: a row's cnt codes in ascending order, then zeros (all 32 zero where cnt = 0xFFFF).  The list always holds the row's fp32
+ * first-min, but WHICH other codes it holds may differ from run to run: a code is kept when it is under the row's threshold at the moment
+ * its tile is scanned, and the waves that tighten the threshold run concurrently (a few more exact evaluations, never a lost minimum). */
 int femasr_vq_candidates(void *stream, const float *z, int64_t M, int D, const void *aux, const float *ee, int n_e,
                          uint16_t *cand, uint16_t *cnt);
 int femasr_codebook_gather(void *stream, const int64_t *idx, int64_t M, int D, const float *cb, int n_e, float *zq);
