@@ -34,6 +34,13 @@ inline int femasr_allow_dynamic_lds(const void *kern, unsigned long long *devs, 
 }
 #define FEMASR_CHECK(expr) do { const int _rc = (expr); if (_rc != FEMASR_OK) return _rc; } while (0)
 
+// blocks of 256 threads for a grid-stride weight repack of `total` items: at most 4096, at least one
+inline unsigned repack_grid(size_t total)
+{
+    const size_t g = (total + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
 // conv launcher with the VQ-argmin epilogue option (kernels_conv.hip)
 //   vq_part != nullptr : instead of storing the tile, each block writes, per row, the
 //   first-min (distance, column) over its BN columns of d = (vq_zz[row] + vq_ee[col]) - 2*acc

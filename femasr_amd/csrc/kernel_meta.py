@@ -3,12 +3,15 @@
     python femasr_amd/csrc/kernel_meta.py [--table out.txt]        # print the table; exit 1 if a kernel outside ALLOW_SCRATCH uses scratch
     python femasr_amd/csrc/kernel_meta.py --diff OTHER_CSRC_DIR [--rename OLD=NEW ...]
                                                                    # device code of the objects built here against those of another build
-                                                                   # (a refactor must leave it alone); exit 1 if a kernel differs
+                                                                   # (a refactor must leave it alone); exit 1 if a kernel differs;
+                                                                   # under each that does: both builds' registers / spills / LDS,
+                                                                   # instruction counts, and whether its MFMA loops kept their sequence
 
 `build.py` runs `check()` after compiling: a kernel of the DEFAULT launch schedule must not touch scratch memory (spilled VGPRs turn
 into HBM traffic: VERDICT r4 found 228 B per thread in the codebook lookup and accumulator tiles spilled inside a Winograd main loop).
 Opt-in / experiment instantiations are allow-listed by name prefix.
 """
+import functools
 import os
 import re
 import struct
@@ -129,6 +132,7 @@ COUNTED = {'loops': 1, 'global_load_lds_dwordx4': 12, 'global_load_dwordx4': 8, 
 N_GEMM_BF16S = 9                # instantiations (activation x residual operands, + the 3x3 conv form x residual operands)
 
 
+@functools.lru_cache(maxsize=None)
 def disassemble(obj_path):
     """{kernel symbol: [(address, mnemonic, operands)]} of the gfx950 code object inside a hipcc .o."""
     elf = device_elf(obj_path)
@@ -238,12 +242,38 @@ def diff(here, there, rename=()):
     return lines
 
 
+LOOP_PREFIXES = VMEM_PREFIXES + ('ds_', 'v_mfma', 's_waitcnt', 's_barrier')
+
+
+def loop_sequences(insts):
+    """Per MFMA loop of disassemble()'s list, the VMEM, LDS, MFMA, s_waitcnt (with its counts) and s_barrier instructions in order: what a
+    refactor of the code around the loops must not move."""
+    return [[op + (' ' + args if op == 's_waitcnt' else '') for _, op, args in insts[lo:hi + 1] if op.startswith(LOOP_PREFIXES)]
+            for lo, hi in mfma_loops(insts)]
+
+
+def detail(new, old, new_insts, old_insts):
+    """The lines under a kernel that `differs`: metadata and instruction count of both builds (code_of() values), and whether the MFMA loops
+    kept their sequence (disassemble() lists)."""
+    def row(v):
+        return 'vgpr %s agpr %s sgpr %s vspill %s sspill %s scratch %s lds %s, %d instructions' % (v[1] + (len(v[0]),))
+    ln, lo = loop_sequences(new_insts), loop_sequences(old_insts)
+    return ['    here:   ' + row(new), '    parent: ' + row(old),
+            '    MFMA loops %d / %d; VMEM, LDS, MFMA, s_waitcnt and s_barrier sequence inside them: %s' % (len(ln), len(lo), 'unchanged' if ln == lo else 'CHANGED')]
+
+
 if __name__ == '__main__':
     if '--diff' in sys.argv:
         pairs = [tuple(sys.argv[i + 1].split('=', 1)) for i, a in enumerate(sys.argv) if a == '--rename']
-        lines = diff(code_of(HERE), code_of(sys.argv[sys.argv.index('--diff') + 1]), pairs)
+        other = sys.argv[sys.argv.index('--diff') + 1]
+        here, there = code_of(HERE), code_of(other)
+        lines = diff(here, there, pairs)
+        was = {new: old for old, new in pairs}
         for f, n, what in lines:
             print('%-24s %-10s %s' % (f, what, n))
+            if what == 'differs':
+                o = was.get(n, n)
+                print('\n'.join(detail(here[f][n], there[f][o], disassemble(os.path.join(HERE, f))[n], disassemble(os.path.join(other, f))[o])))
         print({w: sum(1 for l in lines if l[2] == w) for w in ('same', 'differs', 'only here', 'only there')})
         sys.exit(1 if any(l[2] == 'differs' for l in lines) else 0)
     rows, bad = check(verbose='--quiet' not in sys.argv)

@@ -25,24 +25,18 @@
 //     cross-tile prefetch - land within 2 % of each other (MFMA busy 0.66-0.74 in the network at 2.4 GHz); ablations
 //     price the epilogue stores at ~10 %, the A and W DMA at 5-8 % each, the barriers at 0.
 //   * Epilogue: bias, exact-erf GELU, up to two residuals (order fixed by the bit-exact contract), each 32 x 32 tile
-//     transposed through a per-wave LDS scratch and stored as float4 rows; or the VQ first-min epilogue.
-#include "conv_common.h"
+//     transposed through a per-wave LDS scratch and stored as float4 rows (gemm_store_epilogue, gemm_common.h, which also holds the
+//     block decode and the host side the three row GEMMs share); or the VQ first-min epilogue.
+#include "gemm_common.h"
 #include <type_traits>
 #include <atomic>
-#include "detmath.h"
-#include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-struct GemmParams {
-    const float *A, *W, *bias, *res1, *res2;
-    float *out;
-    const float *vq_zz, *vq_ee;
+struct GemmDmaParams : GemmParams {
+    const float *vq_zz, *vq_ee;  // the VQ epilogue
     float *vq_part;
     int vq_nblk;
-    int M, N, K, nchunks, MB, NB, NT32;
 };
 
 // Configuration <WT, KB, ST>: WT = accumulator tiles (32 x 32) per wave and dimension - the block (4 waves, 2 x 2) computes
@@ -68,7 +62,7 @@ __device__ __forceinline__ void dma16(const float *gsrc, float *lds_dst_uniform)
 }
 
 template <int WT, int KB, int ST, int ACT, int NRES, bool VQ>
-__global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dma_kernel(const GemmParams p)
+__global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dma_kernel(const GemmDmaParams p)
 {
     using C = GCfg<WT, KB, ST>;
     constexpr int G_BM = C::kBM, G_BN = C::kBM;
@@ -83,13 +77,8 @@ __global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dm
     static_assert(!VQ || WT == 2, "the VQ epilogue reduces over 128-column blocks");
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB, mb = L / p.NB;
-    const int m0 = mb * G_BM, n0 = nb * G_BN;
-    const int h = lane >> 5, c31 = lane & 31;
+    const GemmFrame f(p.MB, p.NB, G_BM);
+    const int t = f.t, lane = f.lane, wave = f.wave, wm = f.wm, wn = f.wn, nb = f.nb, m0 = f.m0, n0 = f.n0, h = f.h, c31 = f.c31;
 
     // ---- DMA sources.  A piece i of this wave = rows RPP*(PP*wave+i) .. of the tile: lane -> (row, granule).
     const float *srcA[PP];
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dm
     // ONE column tile (WT = 2: tile `wave`, all its j; WT = 1: tile wave/2, j = 2*(wave&1) + {0,1}).
     int ntile = (n0 >> 5) + (PP * wave) / KB;
     ntile = ntile < p.NT32 ? ntile : p.NT32 - 1;            // tiles past the packed matrix: clamp (never stored)
-    const float *srcW = p.W + ((size_t)ntile * 256 + lane) * 4 + ((PP * wave) % KB) * 256;
+    const float *srcW = static_cast<const float *>(p.W) + ((size_t)ntile * 256 + lane) * 4 + ((PP * wave) % KB) * 256;
     const size_t wchunk = (size_t)p.NT32 * 1024;            // floats per 32-deep K chunk of the packed matrix
 
     auto issue = [&](int sb, int c) {
@@ -202,67 +191,7 @@ __global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dm
     asm volatile("" ::: "memory");
 
     if constexpr (!VQ) {
-        // out = act(acc + bias) + res1 + res2, in that order (bit-exact contract).  Each 32x32 tile goes through a
-        // per-wave LDS scratch so that lane l owns columns 4(l&7)..+3 of tile rows (l>>3) + 8k: float4 loads / stores.
-        float *T = smem + wave * TSCRATCH;
-        const int trow = lane >> 3, tq = lane & 7;
-        const float *ra = p.res1 ? p.res1 : p.res2, *rb = (p.res1 && p.res2) ? p.res2 : nullptr;
-        const bool vec = (p.N & 3) == 0;
-#pragma unroll
-        for (int tl = 0; tl < WT * WT; ++tl) {
-            const int i = tl / WT, j = tl % WT;
-            const int rbase = m0 + (wm * WT + i) * 32, cbase = n0 + (wn * WT + j) * 32;
-            if (vec) {
-                const int col = cbase + 4 * tq;
-                const bool cok = col < p.N;
-                f32x4_t r1[4], r2[4];
-                if (NRES >= 1) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int row = rbase + trow + 8 * k;
-                        const bool ok = cok && row < p.M;
-                        const size_t o = ok ? (size_t)row * p.N + col : 0;
-                        r1[k] = *reinterpret_cast<const f32x4_t *>(ra + o);
-                        if (NRES >= 2) r2[k] = *reinterpret_cast<const f32x4_t *>(rb + o);
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * h) * TPITCH + c31] = acc[i][j][r];
-                const f32x4_t b4 = *reinterpret_cast<const f32x4_t *>(p.bias + (cok ? col : 0));
-                // (same wave wrote and reads the scratch: LDS ops of one wave complete in order)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const f32x4_t a4 = *reinterpret_cast<const f32x4_t *>(T + (trow + 8 * k) * TPITCH + 4 * tq);
-                    float v[4] = {a4[0] + b4[0], a4[1] + b4[1], a4[2] + b4[2], a4[3] + b4[3]};
-                    if (ACT == FEMASR_ACT_GELU) {         // two at a time on the packed fp32 ALU (bit-identical per element)
-                        const det_f32x2 g0 = det_gelu2(det_f32x2{v[0], v[1]}), g1 = det_gelu2(det_f32x2{v[2], v[3]});
-                        v[0] = g0[0]; v[1] = g0[1]; v[2] = g1[0]; v[3] = g1[1];
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if (NRES >= 1) v[e] = v[e] + r1[k][e];
-                        if (NRES >= 2) v[e] = v[e] + r2[k][e];
-                    }
-                    const int row = rbase + trow + 8 * k;
-                    if (cok && row < p.M)
-                        *reinterpret_cast<f32x4_t *>(p.out + (size_t)row * p.N + col) = f32x4_t{v[0], v[1], v[2], v[3]};
-                }
-            } else {
-                const int col = cbase + c31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row < p.M && col < p.N) {
-                        const size_t o = (size_t)row * p.N + col;
-                        float v = acc[i][j][r] + p.bias[col];
-                        if (ACT == FEMASR_ACT_GELU) v = det_gelu(v);
-                        if (NRES >= 1) v = v + ra[o];
-                        if (NRES >= 2) v = v + rb[o];
-                        p.out[o] = v;
-                    }
-                }
-            }
-        }
+        gemm_store_epilogue<WT, ACT, NRES, false>(p, f, smem, [&](int i, int j, int r) { return acc[i][j][r]; });
     } else if constexpr (WT == 2) {
         // d = (|z|^2 + |e|^2) - 2 z.e ; first-min over this block's 128 columns, per row (femasr_arch.py:35-38,63-66).
         float *red = smem;   // [2 (wn)][128 rows][2]  (2 KB)
@@ -308,13 +237,6 @@ __global__ __launch_bounds__(256, (GCfg<WT, KB, ST>::kBlocksPerCU)) void gemm_dm
     }
 }
 
-struct GVariant {
-    const char *name;
-    void (*kern)(const GemmParams);
-    int lds;
-    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d
-};
-
 #define G_VARIANT(WT, KB, ST, ACT, NRES, VQ) { "gemm_dma<tile=64*" #WT ",k=8*" #KB ",stages=" #ST ",act=" #ACT ",nres=" #NRES ",vq=" #VQ ">", \
                                                 gemm_dma_kernel<WT, KB, ST, ACT, NRES, VQ>, GCfg<WT, KB, ST>::kLdsBytes, 0ull }
 #define G_CFG(WT, KB, ST, VQ) G_VARIANT(WT, KB, ST, 0, 0, false), G_VARIANT(WT, KB, ST, 0, 1, false), G_VARIANT(WT, KB, ST, 0, 2, false), \
@@ -323,7 +245,7 @@ struct GVariant {
 // (the 64 x 64 configuration has no VQ form: slot unused.  Measured and dropped again: 64 x 64 with 3 / 4 stages and 128 x 128 with
 // four 16-deep stages - G_CFG(1, 4, 3) / (1, 4, 4) / (2, 2, 4) - are within +-3 % of these at every batch size: prefetch depth is
 // not what bounds the kernel)
-GVariant g_gv[] = { G_CFG(2, 4, 2, true), G_CFG(2, 2, 3, true), G_CFG(1, 4, 2, false) };
+GemmVariant<GemmDmaParams> g_gv[] = { G_CFG(2, 4, 2, true), G_CFG(2, 2, 3, true), G_CFG(1, 4, 2, false) };
 constexpr int kPerCfg = 7;
 constexpr int kTileOf[] = { 128, 128, 64 };
 constexpr int kNumG = sizeof(g_gv) / sizeof(g_gv[0]);
@@ -361,9 +283,7 @@ int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out)
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 32) == 0, "repack_k1: bad args");
     const size_t total = (size_t)I * ((O + 31) / 32) * 32;
-    size_t g = (total + 255) / 256;
-    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);
-    hipLaunchKernelGGL(repack_k1_kernel, dim3((unsigned)g), dim3(256), 0, s, in, O, I, out, total);
+    hipLaunchKernelGGL(repack_k1_kernel, dim3(repack_grid(total)), dim3(256), 0, s, in, O, I, out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }
@@ -402,26 +322,13 @@ int femasr_gemm_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq_e
 {
     FEMASR_REQUIRE(a && a->in && a->w && femasr_gemm_eligible(a), "gemm: layer is not a 1x1 / linear layer with Cin %% 32 == 0");
     FEMASR_REQUIRE(vq || (a->bias && a->out), "gemm: bias/out must be set");
-    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm: bad activation %d", a->act);
-    const long long M = (long long)a->B * a->H * a->W;
-    FEMASR_REQUIRE(a->Ho == a->H && a->Wo == a->W, "gemm: Ho/Wo mismatch");
-    FEMASR_REQUIRE(M > 0 && M < (1ll << 31) - 256, "gemm: bad row count");
-    GemmParams p{};
-    p.A = a->in; p.W = a->w; p.bias = a->bias; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.M = (int)M; p.N = a->Cout; p.K = a->Cin; p.nchunks = a->Cin / 32;
-    p.NT32 = (p.N + 31) / 32;
+    GemmDmaParams p{};
+    FEMASR_CHECK(gemm_params(a, "gemm", a->H, a->W, a->Cin, p));
+    p.W = a->w;
     if (vq) {
         FEMASR_REQUIRE(vq->zz && vq->ee && vq->part && vq->nblk == (p.N + 127) / 128 && (a->Cout % 32) == 0, "vq epilogue: bad args");
         p.vq_zz = vq->zz; p.vq_ee = vq->ee; p.vq_part = vq->part; p.vq_nblk = vq->nblk;
     }
     const int vi = femasr_gemm_pick_variant(a, vq != nullptr);
-    const int bt = kTileOf[vi / kPerCfg];
-    p.MB = (p.M + bt - 1) / bt; p.NB = (p.N + bt - 1) / bt;
-    GVariant &v = g_gv[vi];
-    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, (size_t)v.lds));
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(256), (size_t)v.lds, s, p);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    if (variant_out) *variant_out = vi;
-    if (flops_out) *flops_out = 2.0 * (double)M * (double)a->Cout * (double)a->Cin;
-    return FEMASR_OK;
+    return gemm_variant_launch(s, g_gv, vi, kTileOf[vi / kPerCfg], p, variant_out, flops_out);
 }

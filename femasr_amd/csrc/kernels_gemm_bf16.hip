@@ -39,23 +39,15 @@
 // compiler waits for vmcnt(0) at the first LDS access and sinks the copies below the compute).  The counts are only right if the
 // compiler emits NO VMEM instruction of its own between them: csrc/kernel_meta.py check_counted_waits() disassembles these kernels
 // after every build and fails it otherwise (tests/test_host_logic.py::test_counted_waits_of_the_split_gemm).
-#include "conv_common.h"
-#include "detmath.h"
-#include <stdlib.h>
+#include "gemm_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
-struct GemmSParams {
-    const float *A;
-    const uint4 *W;          // femasr_repack_k1_bf16s
-    const float *bias, *res1, *res2;
-    float *out;
-    int M, N, K, MB, NB, NT32;
+struct GemmSParams : GemmParams {
     int imH, imW, Cin, tapmul;   // CONV form: input image size, channels per tap, ceil(2^20 / (Cin / 32)) (chunk -> tap without a division)
     int imHo, imWo, stride;      // ... output image size, stride (1 or 2)
 };
@@ -119,19 +111,14 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16s_kernel(const GemmSParams p)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint4 *S = reinterpret_cast<uint4 *>(smem_raw);
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB, mb = L / p.NB;
-    const int m0 = mb * 128, n0 = nb * 128;
-    const int h = lane >> 5, c31 = lane & 31;
+    const GemmFrame f(p.MB, p.NB, 128);
+    const int t = f.t, lane = f.lane, wave = f.wave, wm = f.wm, wn = f.wn, m0 = f.m0, n0 = f.n0, h = f.h, c31 = f.c31;
     const int nsteps = p.K >> 4;
 
     // ---- W pieces of this wave: column tile `wave` of the block, 3 pieces (planes) per step, contiguous in the pack
     int ntile = (n0 >> 5) + wave;
     ntile = ntile < p.NT32 ? ntile : p.NT32 - 1;            // tiles past the packed matrix: clamp (never stored)
-    const uint4 *srcW = p.W + (size_t)ntile * 192 + lane;
+    const uint4 *srcW = static_cast<const uint4 *>(p.W) + (size_t)ntile * 192 + lane;
     const size_t wstep = (size_t)p.NT32 * 192;              // uint4 per step
     const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_vptr_s)S);
 
@@ -273,8 +260,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16s_kernel(const GemmSParams p)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     float *T = reinterpret_cast<float *>(smem_raw) + wave * TSCRATCH;
     {
-        // fp32 output: lane l owns columns 4 (l & 7) .. +3 of tile rows (l >> 3) + 8 k: float4 loads / stores (the epilogue of kernels_gemm.hip).
-        // Bias (two column tiles) and the residual rows of the first tile are requested BEFORE the last barrier, the residuals of tile t + 1 before
+        // The store epilogue described in gemm_common.h, on hi + lo: this is the second copy of gemm_store_epilogue (same arithmetic, same
+        // guards; the header says why it is written out) - change both together.  What differs is the fetch order: bias (two column tiles) and the residual rows of the first tile are requested BEFORE the last barrier, the residuals of tile t + 1 before
         // tile t is processed: one exposed round trip per block instead of one per tile (profiles/r05_gemm_bf16s_ubench.txt).
         const int trow = lane >> 3, tq = lane & 7;
         const float *ra = p.res1 ? p.res1 : p.res2, *rb = (p.res1 && p.res2) ? p.res2 : nullptr;
@@ -349,47 +336,38 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16s_kernel(const GemmSParams p)
     }
 }
 
-// [step][n/32][plane][lane] x 8 bf16  <-  W[n][k] (torch (out, in)), zero padded in n;
-// lane (j = lane & 31, h = lane >> 5) holds k = 16 step + 8 h + 0..7 of column n = 32 (n/32) + j.
-__global__ void repack_k1_bf16s_kernel(const float *__restrict__ in, int O, int I, uint4 *__restrict__ out, size_t total)
+// [step][n/32][plane][lane] x 8 bf16  <-  the eight floats GATHER reads for (column n, k0 .. k0 + 7), zero padded in n (frag_item, gemm_common.h).
+// The two gathers, from W[n][k]: a torch (out, in) matrix, K = I ...
+struct GatherOI {
+    static __device__ __forceinline__ void load(const float *in, int I, int n, int k0, f32x4_t &u, f32x4_t &v)
+    {
+        u = *reinterpret_cast<const f32x4_t *>(in + (size_t)n * I + k0);
+        v = *reinterpret_cast<const f32x4_t *>(in + (size_t)n * I + k0 + 4);
+    }
+};
+// ... and a 3x3 conv weight (O, I, 3, 3), tap-major: K = 9 I with k = (3 ky + kx) I + c
+struct GatherOIHW3x3 {
+    static __device__ __forceinline__ void load(const float *in, int I, int n, int k0, f32x4_t &u, f32x4_t &v)
+    {
+        const int tap = k0 / I, c0 = k0 - tap * I;                  // (8 consecutive channels of one tap: I % 16 == 0)
+        float w[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) w[j] = in[((size_t)n * I + c0 + j) * 9 + tap];
+        u = f32x4_t{w[0], w[1], w[2], w[3]};
+        v = f32x4_t{w[4], w[5], w[6], w[7]};
+    }
+};
+template <class GATHER>
+__global__ void repack_bf16s_kernel(const float *__restrict__ in, int O, int I, uint4 *__restrict__ out, size_t total)
 {
     const int NT32 = (O + 31) / 32;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t rest = i >> 6;
-        const int nt = (int)(rest % NT32), st = (int)(rest / NT32);
-        const int n = 32 * nt + (lane & 31), k0 = 16 * st + 8 * (lane >> 5);
+        const FragItem it = frag_item(i, NT32);
         f32x4_t u = {0.f, 0.f, 0.f, 0.f}, v = {0.f, 0.f, 0.f, 0.f};
-        if (n < O) {
-            u = *reinterpret_cast<const f32x4_t *>(in + (size_t)n * I + k0);
-            v = *reinterpret_cast<const f32x4_t *>(in + (size_t)n * I + k0 + 4);
-        }
+        if (it.n < O) GATHER::load(in, I, it.n, it.k0, u, v);
         uint4 q1, q2, q3;
         split3_x8(u, v, q1, q2, q3);
-        uint4 *o = out + ((size_t)st * NT32 + nt) * 192 + lane;
-        o[0] = q1;
-        o[64] = q2;
-        o[128] = q3;
-    }
-}
-
-// the same pack for a 3x3 conv weight (O, I, 3, 3): K = 9 I with k = (3 ky + kx) I + c
-__global__ void repack_oihw_bf16s_kernel(const float *__restrict__ in, int O, int I, uint4 *__restrict__ out, size_t total)
-{
-    const int NT32 = (O + 31) / 32;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t rest = i >> 6;
-        const int nt = (int)(rest % NT32), st = (int)(rest / NT32);
-        const int n = 32 * nt + (lane & 31), k0 = 16 * st + 8 * (lane >> 5);
-        const int tap = k0 / I, c0 = k0 - tap * I;                  // (8 consecutive channels of one tap: I % 16 == 0)
-        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (n < O)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = in[((size_t)n * I + c0 + j) * 9 + tap];
-        uint4 q1, q2, q3;
-        split3_x8(f32x4_t{v[0], v[1], v[2], v[3]}, f32x4_t{v[4], v[5], v[6], v[7]}, q1, q2, q3);
-        uint4 *o = out + ((size_t)st * NT32 + nt) * 192 + lane;
+        uint4 *o = out + it.tile * 192 + it.lane;
         o[0] = q1;
         o[64] = q2;
         o[128] = q3;
@@ -414,14 +392,9 @@ __global__ void mfma_bf16_probe_kernel(const unsigned short *__restrict__ a, con
         if ((r & 3) + 8 * (r >> 2) + 4 * h == i && n < N) d[n] = acc[r];
 }
 
-struct GSVariant {
-    const char *name;
-    void (*kern)(const GemmSParams);
-    unsigned long long attr_devs;       // bit d: MaxDynamicSharedMemorySize set on device d
-};
-#define GS_VARIANT(ACT, NRES) { "gemm_bf16s<act=" #ACT ",nres=" #NRES ">", gemm_bf16s_kernel<ACT, NRES, 0>, 0ull }
-#define GC_VARIANT(NRES) { "conv3x3_bf16s<128px x128,9Cin split GEMM,nres=" #NRES ">", gemm_bf16s_kernel<0, NRES, 1>, 0ull }
-GSVariant g_gsv[] = { GS_VARIANT(0, 0), GS_VARIANT(0, 1), GS_VARIANT(0, 2), GS_VARIANT(1, 0), GS_VARIANT(1, 1), GS_VARIANT(1, 2),
+#define GS_VARIANT(ACT, NRES) { "gemm_bf16s<act=" #ACT ",nres=" #NRES ">", gemm_bf16s_kernel<ACT, NRES, 0>, GS_LDS_BYTES, 0ull }
+#define GC_VARIANT(NRES) { "conv3x3_bf16s<128px x128,9Cin split GEMM,nres=" #NRES ">", gemm_bf16s_kernel<0, NRES, 1>, GS_LDS_BYTES, 0ull }
+GemmVariant<GemmSParams> g_gsv[] = { GS_VARIANT(0, 0), GS_VARIANT(0, 1), GS_VARIANT(0, 2), GS_VARIANT(1, 0), GS_VARIANT(1, 1), GS_VARIANT(1, 2),
                       GC_VARIANT(0), GC_VARIANT(1), GC_VARIANT(2) };      // 6 + residual operands: the 3x3 conv form
 constexpr int kNumGS = sizeof(g_gsv) / sizeof(g_gsv[0]);
 
@@ -442,28 +415,26 @@ bool femasr_conv3x3_bf16s_shape_ok(const femasr_conv_args *a)
 int femasr_gemm_bf16s_variant_count() { return kNumGS; }
 const char *femasr_gemm_bf16s_variant_name(int v) { return (v >= 0 && v < kNumGS) ? g_gsv[v].name : "?"; }
 
-extern "C" int femasr_repack_k1_bf16s(void *stream, const float *in, int O, int I, void *out)
+template <class GATHER>
+static int repack_bf16s(void *stream, const float *in, int O, int I, int K, void *out)
 {
-    hipStream_t s = (hipStream_t)stream;
-    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 64) == 0, "repack_k1_bf16s: bad args");
-    const size_t total = (size_t)(I / 16) * ((O + 31) / 32) * 64;
-    size_t g = (total + 255) / 256;
-    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);
-    hipLaunchKernelGGL(repack_k1_bf16s_kernel, dim3((unsigned)g), dim3(256), 0, s, in, O, I, (uint4 *)out, total);
+    const size_t total = (size_t)(K / 16) * ((O + 31) / 32) * 64;
+    hipLaunchKernelGGL(repack_bf16s_kernel<GATHER>, dim3(repack_grid(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, (uint4 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
+}
+
+extern "C" int femasr_repack_k1_bf16s(void *stream, const float *in, int O, int I, void *out)
+{
+    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 64) == 0, "repack_k1_bf16s: bad args");
+    return repack_bf16s<GatherOI>(stream, in, O, I, I, out);
 }
 
 extern "C" size_t femasr_packed_weight_conv3x3_bf16s_bytes(int O, int I) { return femasr_packed_weight_bf16s_bytes(O, 9 * I); }
 extern "C" int femasr_repack_oihw_bf16s(void *stream, const float *in, int O, int I, void *out)
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 64) == 0, "repack_oihw_bf16s: needs a 3x3 OIHW weight with I %% 64 == 0");
-    const size_t total = (size_t)(9 * I / 16) * ((O + 31) / 32) * 64;
-    size_t g = (total + 255) / 256;
-    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);
-    hipLaunchKernelGGL(repack_oihw_bf16s_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, in, O, I, (uint4 *)out, total);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    return FEMASR_OK;
+    return repack_bf16s<GatherOIHW3x3>(stream, in, O, I, 9 * I, out);
 }
 
 extern "C" int femasr_debug_mfma_bf16(void *stream, const uint16_t *a, const uint16_t *b, const float *c, int n, float *d)
@@ -485,24 +456,11 @@ int femasr_gemm_bf16s_launch(hipStream_t s, const femasr_conv_args *a, const voi
 {
     FEMASR_REQUIRE(a && a->in && w_bf16s && femasr_gemm_bf16s_shape_ok(a), "gemm_bf16s: layer is neither a 1x1 / linear layer nor a 3x3 pad-1 conv of stride 1 or 2 with Cin %% 64 == 0");
     FEMASR_REQUIRE(a->bias && a->out, "gemm_bf16s: bias/out must be set");
-    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm_bf16s: bad activation %d", a->act);
     const bool conv = a->ksz == 3;
     const int Ho = conv ? (a->H - 1) / a->stride + 1 : a->H, Wo = conv ? (a->W - 1) / a->stride + 1 : a->W;      // (H + 2 - 3) / stride + 1
-    const long long M = (long long)a->B * Ho * Wo;
-    FEMASR_REQUIRE(a->Ho == Ho && a->Wo == Wo, "gemm_bf16s: Ho/Wo mismatch");
-    FEMASR_REQUIRE(M > 0 && M < (1ll << 31) - 256, "gemm_bf16s: bad row count");
     GemmSParams p{};
-    p.A = a->in; p.W = (const uint4 *)w_bf16s; p.bias = a->bias; p.res1 = a->res1; p.res2 = a->res2; p.out = a->out;
-    p.M = (int)M; p.N = a->Cout; p.K = conv ? 9 * a->Cin : a->Cin;
+    FEMASR_CHECK(gemm_params(a, "gemm_bf16s", Ho, Wo, conv ? 9 * a->Cin : a->Cin, p));
+    p.W = w_bf16s;
     p.imH = a->H; p.imW = a->W; p.imHo = Ho; p.imWo = Wo; p.stride = a->stride; p.Cin = a->Cin; p.tapmul = ((1 << 20) + (a->Cin >> 5) - 1) / (a->Cin >> 5);
-    p.NT32 = (p.N + 31) / 32;
-    p.MB = (p.M + 127) / 128; p.NB = (p.N + 127) / 128;
-    const int vi = femasr_gemm_bf16s_pick_variant(a);
-    GSVariant &v = g_gsv[vi];
-    FEMASR_CHECK(femasr_allow_dynamic_lds((const void *)v.kern, &v.attr_devs, GS_LDS_BYTES));
-    hipLaunchKernelGGL(v.kern, dim3((unsigned)(p.MB * p.NB)), dim3(256), (size_t)GS_LDS_BYTES, s, p);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    if (variant_out) *variant_out = vi;
-    if (flops_out) *flops_out = 2.0 * (double)M * (double)a->Cout * (double)p.K;
-    return FEMASR_OK;
+    return gemm_variant_launch(s, g_gsv, femasr_gemm_bf16s_pick_variant(a), 128, p, variant_out, flops_out);
 }

@@ -9,7 +9,7 @@
 //   w16 = fp16_rne(w)                   packed once by femasr_repack_k1_f16; fp16 subnormals take part with their value
 //   out = epi(bias + sum_k a16_k w16_k) products exact in fp32 (11 + 11 significand bits), accumulated in fp32 by
 //                                       v_mfma_f32_32x32x16_f16, k ascending; bias in fp32; GELU by det_gelu2 - the device function of
-//                                       the split GEMM's epilogue -; one residual added in fp32; stored as fp32.
+//                                       every GEMM epilogue (gemm_common.h) -; one residual added in fp32; stored as fp32.
 //
 // The kernel is memory-side at the network's shapes (M = 82 944 rows, K and N in 256..1024: 8 MFMAs per wave against 16 KiB of fp32
 // rows per 64-deep chunk), so it is built for bytes in flight, not for MFMA scheduling: no inline asm, no counted waits.
@@ -19,22 +19,12 @@
 //     ([128 rows][72 halves]: the 144-byte pitch keeps the 16-lane ds_read_b128 groups conflict-free); one barrier per chunk;
 //   * W: fp16 fragments, fragment-major ([k step][n / 32][lane] x 8 halves: every wave-level load is one contiguous KiB), read from
 //     global / L2 straight into registers two k steps ahead - the whole matrix is at most 512 KiB and stays in L2.
-// 36 KiB of LDS; the epilogue (the split GEMM's: per-wave LDS transpose, float4 loads / stores) overlays the A buffers.
-#include "conv_common.h"
-#include "detmath.h"
+// 36 KiB of LDS; the epilogue (gemm_store_epilogue of gemm_common.h: per-wave LDS transpose, float4 loads / stores) overlays the A buffers.
+#include "gemm_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-struct GemmHParams {
-    const float *A;
-    const uint4 *W;          // femasr_repack_k1_f16
-    const float *bias, *res;
-    float *out;
-    int M, N, K, MB, NB, NT32;
-};
 
 constexpr int GH_CK = 64;                             // K chunk
 constexpr int GH_PITCH = 72;                          // halves per staged row (64 + 8 pad)
@@ -44,18 +34,13 @@ static_assert(4 * TSCRATCH * 4 <= GH_LDS_BYTES, "epilogue scratch overlays the m
 
 template <int ACT, int NRES>
 // (130 VGPRs: three blocks per CU; a bound of four waves per SIMD spills 7 - 9 dwords to scratch, which the build gate refuses)
-__global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmHParams p)
+__global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned short *As = reinterpret_cast<unsigned short *>(smem_raw);      // [2][128][GH_PITCH]
 
-    const int t = threadIdx.x, lane = t & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int L = xcd_remap(blockIdx.x, p.MB * p.NB);
-    const int nb = L % p.NB, mb = L / p.NB;
-    const int m0 = mb * 128, n0 = nb * 128;
-    const int h = lane >> 5, c31 = lane & 31;
+    const GemmFrame f(p.MB, p.NB, 128);
+    const int t = f.t, lane = f.lane, wm = f.wm, wn = f.wn, m0 = f.m0, n0 = f.n0, h = f.h, c31 = f.c31;
     const int nch = p.K / GH_CK, nsteps = p.K >> 4;
 
     // ---- A staging: rows (t >> 4) + 16 i, channels 4 (t & 15) .. + 3 of the chunk; tail rows are clamped (computed, never stored)
@@ -82,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmHParams p)
     // ---- W fragments of this wave's two column tiles: [k step][n / 32][lane]; tiles past the packed matrix are clamped (never stored)
     const uint4 *wl[2];
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) wl[ct] = p.W + ((size_t)wtile(n0, wn * 2 + ct, p.NT32) * 64 + lane);
+    for (int ct = 0; ct < 2; ++ct) wl[ct] = static_cast<const uint4 *>(p.W) + ((size_t)wtile(n0, wn * 2 + ct, p.NT32) * 64 + lane);
     const size_t wstep = (size_t)p.NT32 * 64;          // uint4 per k step
 
     f32x16 acc[2][2];
@@ -131,60 +116,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmHParams p)
         __syncthreads();
     }
 
-    // ---- epilogue: out = act(acc + bias) + res, in that order.  Each 32 x 32 tile goes through a per-wave LDS scratch: lane l owns columns
-    // 4 (l & 7) .. + 3 of tile rows (l >> 3) + 8 k: float4 loads / stores.  (The last barrier of the loop has passed: the A buffers are dead.)
-    float *T = reinterpret_cast<float *>(smem_raw) + wave * TSCRATCH;
-    const int trow = lane >> 3, tq = lane & 7;
-    const bool vec = (p.N & 3) == 0;
-#pragma unroll
-    for (int tl = 0; tl < 4; ++tl) {
-        const int i = tl >> 1, j = tl & 1;
-        const int rbase = m0 + (wm * 2 + i) * 32, cbase = n0 + (wn * 2 + j) * 32;
-        if (vec) {
-            const int col = cbase + 4 * tq;
-            const bool cok = col < p.N;
-            f32x4_t b4 = {0.f, 0.f, 0.f, 0.f}, r4[4] = {};
-            if (p.bias && cok) b4 = *reinterpret_cast<const f32x4_t *>(p.bias + col);
-            if (NRES == 1) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int row = rbase + trow + 8 * k;
-                    if (cok && row < p.M) r4[k] = *reinterpret_cast<const f32x4_t *>(p.res + (size_t)row * p.N + col);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * h) * TPITCH + c31] = acc[i][j][r];
-            // (same wave wrote and reads the scratch: LDS ops of one wave complete in order)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4_t a4 = *reinterpret_cast<const f32x4_t *>(T + (trow + 8 * k) * TPITCH + 4 * tq);
-                float v[4] = {a4[0] + b4[0], a4[1] + b4[1], a4[2] + b4[2], a4[3] + b4[3]};
-                if (ACT == FEMASR_ACT_GELU) {
-                    const det_f32x2 g0 = det_gelu2(det_f32x2{v[0], v[1]}), g1 = det_gelu2(det_f32x2{v[2], v[3]});
-                    v[0] = g0[0]; v[1] = g0[1]; v[2] = g1[0]; v[3] = g1[1];
-                }
-                if (NRES == 1) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] + r4[k][e];
-                }
-                const int row = rbase + trow + 8 * k;
-                if (cok && row < p.M) *reinterpret_cast<f32x4_t *>(p.out + (size_t)row * p.N + col) = f32x4_t{v[0], v[1], v[2], v[3]};
-            }
-        } else {
-            const int col = cbase + c31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row < p.M && col < p.N) {
-                    const size_t o = (size_t)row * p.N + col;
-                    float v = acc[i][j][r] + (p.bias ? p.bias[col] : 0.f);
-                    if (ACT == FEMASR_ACT_GELU) v = det_gelu(v);
-                    if (NRES == 1) v = v + p.res[o];
-                    p.out[o] = v;
-                }
-            }
-        }
-    }
+    // ---- epilogue (gemm_common.h); a null bias adds +0.  (The last barrier of the loop has passed: the A buffers are dead.)
+    gemm_store_epilogue<2, ACT, NRES, true>(p, f, reinterpret_cast<float *>(smem_raw), [&](int i, int j, int r) { return acc[i][j][r]; });
 }
 
 // [k step][n / 32][lane] x 8 halves  <-  W[n][k] (torch (out, in)), zero padded in n, round to nearest even;
@@ -196,10 +129,8 @@ __global__ void repack_k1_f16_kernel(const float *__restrict__ in, int O, int I,
 {
     const int NT32 = (O + 31) / 32;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
-        const size_t rest = i >> 9;
-        const int nt = (int)(rest % NT32), st = (int)(rest / NT32);
-        const int n = 32 * nt + (lane & 31), k = 16 * st + 8 * (lane >> 5) + e;
+        const FragItem it = frag_item(i >> 3, NT32);      // (gemm_common.h)
+        const int n = it.n, nt = n >> 5, k = it.k0 + (int)(i & 7);
         float v = 0.f;
         if (n < O) {
             if (PACKED)      // out[q][ntile][j][lane][t] = W[32 ntile + lane % 32][32 q + 8 j + 4 (lane / 32) + t]  (kernels_gemm.hip)
@@ -211,12 +142,8 @@ __global__ void repack_k1_f16_kernel(const float *__restrict__ in, int O, int I,
     }
 }
 
-struct GHVariant {
-    const char *name;
-    void (*kern)(const GemmHParams);
-};
-#define GH_VARIANT(ACT, NRES) { "gemm_f16<act=" #ACT ",nres=" #NRES ">", gemm_f16_kernel<ACT, NRES> }
-GHVariant g_ghv[] = { GH_VARIANT(0, 0), GH_VARIANT(1, 0), GH_VARIANT(0, 1) };      // what the network uses: qkv / before_quant, fc1, proj / fc2
+#define GH_VARIANT(ACT, NRES) { "gemm_f16<act=" #ACT ",nres=" #NRES ">", gemm_f16_kernel<ACT, NRES>, GH_LDS_BYTES, 0ull }
+GemmVariant<GemmParams> g_ghv[] = { GH_VARIANT(0, 0), GH_VARIANT(1, 0), GH_VARIANT(0, 1) };      // what the network uses: qkv / before_quant, fc1, proj / fc2
 constexpr int kNumGH = sizeof(g_ghv) / sizeof(g_ghv[0]);
 
 template <bool PACKED>
@@ -224,9 +151,7 @@ int repack_k1_f16(hipStream_t s, const float *in, int O, int I, void *out)
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 64) == 0, "repack_k1_f16: needs a (out, in) weight with in %% 64 == 0");
     const size_t total = femasr_packed_weight_k1_f16_bytes(O, I) / sizeof(unsigned short);
-    size_t g = (total + 255) / 256;
-    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);
-    hipLaunchKernelGGL(repack_k1_f16_kernel<PACKED>, dim3((unsigned)g), dim3(256), 0, s, in, O, I, (_Float16 *)out, total);
+    hipLaunchKernelGGL(repack_k1_f16_kernel<PACKED>, dim3(repack_grid(total)), dim3(256), 0, s, in, O, I, (_Float16 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }
@@ -245,24 +170,13 @@ int femasr_gemm_f16_launch(hipStream_t s, const femasr_conv_args *a, int *varian
 {
     FEMASR_REQUIRE(a && a->in && a->w_f16 && femasr_gemm_f16_shape_ok(a), "gemm_f16: not a 1x1 stride-1 layer with Cin %% 64 == 0 and no prologue");
     FEMASR_REQUIRE(a->out, "gemm_f16: out must be set");
-    FEMASR_REQUIRE(a->act == FEMASR_ACT_NONE || a->act == FEMASR_ACT_GELU, "gemm_f16: bad activation %d", a->act);
     const int nres = (a->res1 ? 1 : 0) + (a->res2 ? 1 : 0);
     FEMASR_REQUIRE(nres <= 1 && !(nres && a->act == FEMASR_ACT_GELU),
                    "gemm_f16: the kernel has three epilogues - plain, GELU, one residual -, not act %d with %d residual operands", a->act, nres);
-    const long long M = (long long)a->B * a->H * a->W;
-    FEMASR_REQUIRE(a->Ho == a->H && a->Wo == a->W, "gemm_f16: Ho/Wo mismatch");
-    FEMASR_REQUIRE(M > 0 && M < (1ll << 31) - 256, "gemm_f16: bad row count");
-    GemmHParams p{};
-    p.A = a->in; p.W = (const uint4 *)a->w_f16; p.bias = a->bias; p.res = a->res1 ? a->res1 : a->res2; p.out = a->out;
-    p.M = (int)M; p.N = a->Cout; p.K = a->Cin;
-    p.NT32 = (p.N + 31) / 32;
-    p.MB = (p.M + 127) / 128; p.NB = (p.N + 127) / 128;
-    const int vi = femasr_gemm_f16_pick_variant(a);
-    hipLaunchKernelGGL(g_ghv[vi].kern, dim3((unsigned)(p.MB * p.NB)), dim3(256), (size_t)GH_LDS_BYTES, s, p);
-    FEMASR_CHECK_HIP(hipGetLastError());
-    if (variant_out) *variant_out = vi;
-    if (flops_out) *flops_out = 2.0 * (double)M * (double)a->Cout * (double)p.K;
-    return FEMASR_OK;
+    GemmParams p{};
+    FEMASR_CHECK(gemm_params(a, "gemm_f16", a->H, a->W, a->Cin, p));
+    p.W = a->w_f16;
+    return gemm_variant_launch(s, g_ghv, femasr_gemm_f16_pick_variant(a), 128, p, variant_out, flops_out);
 }
 
 // the fp16 image of a 1x1 layer from its GEMM-layout fp32 image (femasr_repack_oihw, kh = kw = 1): model.hip, first selection of linear_math 2

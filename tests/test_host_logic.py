@@ -214,6 +214,27 @@ def test_kernel_meta_diff_tells_same_from_differs():
     assert got[last] == 'same' and 'old_name' not in got and sorted(got.values()).count('differs') == 2
 
 
+def test_kernel_meta_detail_tells_a_moved_loop_instruction():
+    """The lines kernel_meta.py --diff prints under a kernel that differs: the MFMA loops of a split-GEMM kernel against themselves are
+    `unchanged`; with one LDS read taken out of the loop they are `CHANGED`; one instruction dropped in front of the loop changes nothing."""
+    import sys
+    csrc = os.path.join(ROOT, 'femasr_amd', 'csrc')
+    obj = os.path.join(csrc, 'kernels_gemm_bf16.o')
+    if not os.path.exists(obj) or not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-objdump'):
+        pytest.skip('no built objects / no llvm-objdump here')
+    sys.path.insert(0, csrc)
+    import kernel_meta
+    name, insts = next((n, i) for n, i in sorted(kernel_meta.disassemble(obj).items()) if 'gemm_bf16s_kernel' in n)
+    row = kernel_meta.code_of(csrc, objs=['kernels_gemm_bf16.o'])['kernels_gemm_bf16.o'][name]
+    (lo, hi), = kernel_meta.mfma_loops(insts)
+    seq = kernel_meta.loop_sequences(insts)
+    assert len(seq) == 1 and seq[0].count('s_waitcnt vmcnt(14)') == 2 and 'v_mfma_f32_32x32x16_bf16' in seq[0] and 's_barrier' in seq[0]
+    assert kernel_meta.detail(row, row, insts, insts)[-1].endswith('MFMA loops 1 / 1; VMEM, LDS, MFMA, s_waitcnt and s_barrier sequence inside them: unchanged')
+    victim = next(i for i in range(lo, hi) if insts[i][1].startswith('ds_read'))
+    assert kernel_meta.detail(row, row, insts[:victim] + [(insts[victim][0], 's_nop', '0')] + insts[victim + 1:], insts)[-1].endswith('CHANGED')
+    assert kernel_meta.detail(row, row, insts[1:], insts)[-1].endswith('unchanged')
+
+
 def test_default_schedule_kernels_use_no_scratch():
     """The build gate, as a test: no gfx950 kernel of the default launch schedule touches scratch memory (spilled registers turn into HBM
     traffic: VERDICT r4 found 40 B per thread in the hot Winograd instantiation and 228 B in the codebook search).  Reads the code objects
