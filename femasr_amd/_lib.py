@@ -43,7 +43,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 107      # femasr_version(): (additive, number kept: femasr_png_filter_rgb8; femasr_dihedral_expand / _merge and their _u8 forms; femasr_repack_k1_f16, the ksz = 1 meaning of w_f16, linear_math 2) femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
+ABI_VERSION = 107      # femasr_version(): (additive, number kept: femasr_channels_split_u8 / _merge_u8, femasr_png_filter_u8; femasr_png_filter_rgb8; femasr_dihedral_expand / _merge and their _u8 forms; femasr_repack_k1_f16, the ksz = 1 meaning of w_f16, linear_math 2) femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -147,6 +147,9 @@ SIGNATURES = {
     'femasr_dihedral_merge': (c_int, [vp, vp, vp, c_int, c_int, c_int, c_int, vp]),
     'femasr_dihedral_merge_u8': (c_int, [vp, vp, vp, c_int, c_int, c_int, vp]),
     'femasr_png_filter_rgb8': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
+    'femasr_png_filter_u8': (c_int, [vp, vp, c_int, c_int, c_int, c_int, c_int, vp]),
+    'femasr_channels_split_u8': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, vp]),
+    'femasr_channels_merge_u8': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp, c_int, vp, vp, c_int, vp]),
     'femasr_clock_probe': (c_int, [vp, c_int, vp]),
     'femasr_clock_probe_entries': (c_int, []),
 }

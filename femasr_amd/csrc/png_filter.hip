@@ -1,8 +1,9 @@
-// png_filter.hip — PNG's row filters for 8-bit RGB on gfx950 (femasr_amd/pngio.py): the uint8 (B,H,W,3) images the network
-// returns -> the byte stream PNG deflates, (B,H,1 + 3W): per row one filter-type byte and the 3W residuals.
+// png_filter.hip — PNG's row filters for 8-bit samples on gfx950 (femasr_amd/pngio.py): uint8 (B,H,W,C) images, C = 1 (gray),
+// 2 (gray + alpha), 3 (RGB: what the network returns), 4 (RGBA) -> the byte stream PNG deflates, (B,H,1 + CW): per row one filter-type byte
+// and the CW residuals.  The kernel is a template on the pixel size C (the distance to the left neighbour); C = 3 is femasr_png_filter_rgb8.
 //
-// Definition (pngio.filter_rows; integers only).  n = 3W, raw[y] = the n bytes of row y.  Per byte i, x = raw[y][i]:
-//   a = raw[y][i-3] (0 if i < 3),  b = raw[y-1][i] (0 if y == 0),  c = raw[y-1][i-3] (0 if either is outside)
+// Definition (pngio.filter_image, for C = 3 pngio.filter_rows; integers only).  n = CW, raw[y] = the n bytes of row y.  Per byte i, x = raw[y][i]:
+//   a = raw[y][i-C] (0 if i < C),  b = raw[y-1][i] (0 if y == 0),  c = raw[y-1][i-C] (0 if either is outside)
 //   f0 = x, f1 = x - a, f2 = x - b, f3 = x - ((a + b) >> 1), f4 = x - paeth(a, b, c)   (mod 256)
 //   paeth: p = a + b - c, pa = |p - a|, pb = |p - b|, pc = |p - c|: a if pa <= pb and pa <= pc, else b if pb <= pc, else c
 //   cost_t = sum_i min(f_t[i], 256 - f_t[i]);  adaptive: t* = the smallest t of least cost;  out[y] = [t*, f_t*[0..n)]
@@ -25,17 +26,17 @@
 //
 // Four bytes per instruction: x - y, (a + b) >> 1 are SWAR on dwords, the cost of four residuals is one v_sad_u8 (|r - 128| of r = f ^ 128 is
 // min(f, 256 - f)); Paeth's predictor is per byte.  No workspace, no atomics, no scratch, no allocation, no synchronisation: capture-safe, on
-// the caller's stream.  Offsets between rows and images are 64-bit, inside a row 32-bit (W <= 2^22: n and the cost sums, <= 128 n, fit).
+// the caller's stream.  Offsets between rows and images are 64-bit, inside a row 32-bit (n <= 3 2^22: n and the cost sums, <= 128 n, fit).
 #include "common.h"
 
 namespace {
 
 constexpr int PF_THREADS = 256;
 constexpr int PF_WAVE = 64;
-constexpr int PF_WAVE_ROW = 3072;        // rows of up to this many bytes (W <= 1024): one wave per row
-constexpr int PF_BLOCK_ROW = 24576;      // rows of up to this many bytes (W <= 8192) are resident in a block team's LDS
+constexpr int PF_WAVE_ROW = 3072;        // rows of up to this many bytes (RGB: W <= 1024): one wave per row
+constexpr int PF_BLOCK_ROW = 24576;      // rows of up to this many bytes (RGB: W <= 8192) are resident in a block team's LDS
 constexpr int PF_FRONT = 32;             // LDS bytes in front of the first staged chunk (zero where they stand for bytes left of the row)
-constexpr int PF_MAX_W = 1 << 22;
+constexpr int PF_MAX_ROW = 3 << 22;      // bytes in a row (RGB: W <= 2^22)
 constexpr int PF_ADAPTIVE = 5;
 constexpr uint32_t PF_H = 0x80808080u;
 
@@ -98,7 +99,7 @@ __host__ __device__ __forceinline__ uint32_t pf_valid(int i, int n)
 struct pf_row {
     const uint8_t *in;       // byte 0 of the row
     uint8_t *out;            // byte 0 of the output row (the filter-type byte)
-    int n;                   // 3 W
+    int n;                   // C W
     unsigned so;             // out & 15: chunk k of the row is the aligned 16 bytes at out - so + 16 k = output bytes j = 16 k - so ..
     int nk;                  // chunks that hold a byte of the output row
     bool above;              // y > 0
@@ -147,7 +148,8 @@ __device__ __forceinline__ int pf_stage(uint4 *lds, const uint8_t *row, int lo, 
     return PF_FRONT + (int)s - lo;
 }
 
-// Row bytes i0 - 4 .. i0 + 16 from LDS (row byte 0 at byte `at0`) as x[m] = bytes i0 + 4 m .. and l[m] = bytes i0 + 4 m - 3 ..
+// Row bytes i0 - 4 .. i0 + 16 from LDS (row byte 0 at byte `at0`) as x[m] = bytes i0 + 4 m .. and l[m] = bytes i0 + 4 m - BPP ..
+template <int BPP>
 __device__ __forceinline__ void pf_window(const uint32_t *lds, int at0, int i0, uint32_t x[4], uint32_t l[4])
 {
     const int q = at0 + i0 - 4;                 // >= 12
@@ -164,17 +166,18 @@ __device__ __forceinline__ void pf_window(const uint32_t *lds, int at0, int i0, 
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         x[m] = g[m + 1];
-        l[m] = pf_shift(g[m], g[m + 1], 1);
+        l[m] = pf_shift(g[m], g[m + 1], 4 - BPP);
     }
 }
 
 // Chunk k of the row: x, a, b, c of output bytes j = 16 k - so .. + 16, i.e. row bytes i0 = j - 1 ..
+template <int BPP>
 __device__ __forceinline__ int pf_chunk(const pf_row &r, const pf_seg &sg, const uint32_t *cur, const uint32_t *up, int k, uint32_t x[4], uint32_t a[4],
                                         uint32_t b[4], uint32_t c[4])
 {
     const int i0 = 16 * k - (int)r.so - 1;
-    pf_window(cur, sg.cur0, i0, x, a);
-    pf_window(up, sg.up0, i0, b, c);            // (row 0: whatever the buffer holds, at the current row's offsets)
+    pf_window<BPP>(cur, sg.cur0, i0, x, a);
+    pf_window<BPP>(up, sg.up0, i0, b, c);            // (row 0: whatever the buffer holds, at the current row's offsets)
     const uint32_t keep = r.above ? 0xffffffffu : 0u;
 #pragma unroll
     for (int m = 0; m < 4; ++m) b[m] &= keep, c[m] &= keep;
@@ -189,8 +192,8 @@ struct pf_team {
     static constexpr int LDS16 = (CAP + 128) / 16;                                    // uint4 per staged row: front, the chunks, read-ahead
 };
 
-// filter: 0..4 fixed, 5 adaptive.  rows = B H.
-template <int T>
+// filter: 0..4 fixed, 5 adaptive.  rows = B H.  BPP: bytes per pixel, 1..4.
+template <int T, int BPP>
 __global__ __launch_bounds__(PF_THREADS) void png_filter_kernel(const uint8_t *__restrict__ img, long long rows, int H, int W, int filter,
                                                                  uint8_t *__restrict__ out)
 {
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(PF_THREADS) void png_filter_kernel(const uint8_t *_
     const int team = (int)threadIdx.x / T, lane = (int)threadIdx.x % T;
     const long long row = (long long)blockIdx.x * P::TEAMS + team;
     const bool active = row < rows;                      // (an idle team still meets the block's barriers)
-    const int n = 3 * W;
+    const int n = BPP * W;
     pf_row r;
     r.n = n;
     r.in = img + (size_t)(active ? row : 0) * (size_t)n;
@@ -236,7 +239,7 @@ __global__ __launch_bounds__(PF_THREADS) void png_filter_kernel(const uint8_t *_
             if (active) {
                 for (int k = sg.k0 + lane; k < sg.k1; k += T) {
                     uint32_t x[4], a[4], b[4], c[4];
-                    const int i0 = pf_chunk(r, sg, cur, up, k, x, a, b, c);
+                    const int i0 = pf_chunk<BPP>(r, sg, cur, up, k, x, a, b, c);
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
                         const uint32_t ok = pf_valid(i0 + 4 * m, n);
@@ -285,7 +288,7 @@ __global__ __launch_bounds__(PF_THREADS) void png_filter_kernel(const uint8_t *_
         if (active) {
             for (int k = sg.k0 + lane; k < sg.k1; k += T) {
                 uint32_t x[4], a[4], b[4], c[4], f[4];
-                pf_chunk(r, sg, cur, up, k, x, a, b, c);
+                pf_chunk<BPP>(r, sg, cur, up, k, x, a, b, c);
 #pragma unroll
                 for (int m = 0; m < 4; ++m) f[m] = pf_residual(t, x[m], a[m], b[m], c[m]);
                 const int j0 = 16 * k - (int)r.so;       // output byte of the chunk's byte 0
@@ -315,21 +318,40 @@ __global__ __launch_bounds__(PF_THREADS) void png_filter_kernel(const uint8_t *_
 
 }  // namespace
 
-extern "C" int femasr_png_filter_rgb8(void *stream, const uint8_t *img, int B, int H, int W, int filter, uint8_t *out)
+// what the two entries share; `name`: the entry's, for the messages
+template <int BPP>
+static int pf_launch(const char *name, void *stream, const uint8_t *img, int B, int H, int W, int filter, uint8_t *out)
 {
-    FEMASR_REQUIRE(img && out, "png_filter_rgb8: null argument");
-    FEMASR_REQUIRE(B >= 1 && H >= 1 && W >= 1, "png_filter_rgb8: empty shape: %d images of %dx%d", B, H, W);
-    FEMASR_REQUIRE(filter >= 0 && filter <= PF_ADAPTIVE, "png_filter_rgb8: filter %d is not 0..4 (fixed) or 5 (adaptive)", filter);
-    FEMASR_REQUIRE(W <= PF_MAX_W, "png_filter_rgb8: W = %d is more than 2^22 (32-bit offsets and cost sums inside a row)", W);
+    FEMASR_REQUIRE(img && out, "%s: null argument", name);
+    FEMASR_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: empty shape: %d images of %dx%d", name, B, H, W);
+    FEMASR_REQUIRE(filter >= 0 && filter <= PF_ADAPTIVE, "%s: filter %d is not 0..4 (fixed) or 5 (adaptive)", name, filter);
+    FEMASR_REQUIRE(W <= PF_MAX_ROW / BPP, "%s: a row of W = %d pixels of %d bytes is more than 3 * 2^22 bytes (32-bit offsets and cost sums inside a row)",
+                   name, W, BPP);
     const long long rows = (long long)B * H;
-    FEMASR_REQUIRE(rows <= (1ll << 31) - 1, "png_filter_rgb8: %d images of %d rows are more than 2^31 - 1 rows", B, H);
+    FEMASR_REQUIRE(rows <= (1ll << 31) - 1, "%s: %d images of %d rows are more than 2^31 - 1 rows", name, B, H);
     hipStream_t st = (hipStream_t)stream;
-    if (3 * W <= PF_WAVE_ROW) {
+    if (BPP * W <= PF_WAVE_ROW) {
         const unsigned blocks = (unsigned)((rows + pf_team<PF_WAVE>::TEAMS - 1) / pf_team<PF_WAVE>::TEAMS);
-        hipLaunchKernelGGL(png_filter_kernel<PF_WAVE>, dim3(blocks), dim3(PF_THREADS), 0, st, img, rows, H, W, filter, out);
+        hipLaunchKernelGGL((png_filter_kernel<PF_WAVE, BPP>), dim3(blocks), dim3(PF_THREADS), 0, st, img, rows, H, W, filter, out);
     } else {
-        hipLaunchKernelGGL(png_filter_kernel<PF_THREADS>, dim3((unsigned)rows), dim3(PF_THREADS), 0, st, img, rows, H, W, filter, out);
+        hipLaunchKernelGGL((png_filter_kernel<PF_THREADS, BPP>), dim3((unsigned)rows), dim3(PF_THREADS), 0, st, img, rows, H, W, filter, out);
     }
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
+}
+
+extern "C" int femasr_png_filter_rgb8(void *stream, const uint8_t *img, int B, int H, int W, int filter, uint8_t *out)
+{
+    return pf_launch<3>("png_filter_rgb8", stream, img, B, H, W, filter, out);
+}
+
+extern "C" int femasr_png_filter_u8(void *stream, const uint8_t *img, int B, int H, int W, int C, int filter, uint8_t *out)
+{
+    switch (C) {
+    case 1: return pf_launch<1>("png_filter_u8", stream, img, B, H, W, filter, out);
+    case 2: return pf_launch<2>("png_filter_u8", stream, img, B, H, W, filter, out);
+    case 3: return pf_launch<3>("png_filter_u8", stream, img, B, H, W, filter, out);
+    case 4: return pf_launch<4>("png_filter_u8", stream, img, B, H, W, filter, out);
+    default: return femasr_set_error(FEMASR_ERR_INVALID, "png_filter_u8: C = %d is not 1..4 bytes per pixel", C);
+    }
 }

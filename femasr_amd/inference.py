@@ -70,19 +70,36 @@ def build_parser():
                          'PNG run on the GPU, N threads deflate and write behind the forward (femasr_amd.pngio: the same pixels, not the '
                          'same file bytes), one more thread decodes up to two inputs ahead')
     ap.add_argument('--png-level', type=int, default=6, metavar='0..9', help="deflate level of --io-threads N >= 1 (default 6, PIL's)")
+    ap.add_argument('--keep-format', action='store_true',
+                    help="the output has the input's channels: a gray image (modes L, 1) comes back gray, gray + alpha (LA) and RGBA (also a "
+                         'palette image with transparency) keep their alpha channel (femasr_amd.channels; off by default: every input is '
+                         'converted to RGB and written as RGB)')
+    ap.add_argument('--alpha', choices=['bicubic', 'network'], default='bicubic',
+                    help="with --keep-format, how the alpha channel is upscaled: 'bicubic' (MATLAB bicubic, clipped and rounded) or 'network' "
+                         '(the alpha plane takes the same forward as the colour, without the colour fix)')
     return ap
 
 
-def _decode(path):
+def _decode(path, keep_format=False):
+    """uint8 (H,W,3) RGB.  keep_format: the file's own channels instead - (H,W) for modes L and 1, (H,W,2) for LA, (H,W,4) for RGBA and for
+    a palette image with transparency; a palette image without, and every other mode (RGB, I;16, CMYK, ...): RGB as ever."""
     from PIL import Image
-    return np.array(Image.open(path).convert('RGB'))                      # cv2.imread + BGR2RGB == RGB
+    im = Image.open(path)
+    if keep_format:
+        if im.mode in ('L', '1'):
+            return np.array(im.convert('L'))
+        if im.mode in ('LA', 'RGBA'):
+            return np.array(im)
+        if im.mode == 'P' and 'transparency' in im.info:
+            return np.array(im.convert('RGBA'))
+    return np.array(im.convert('RGB'))                                    # cv2.imread + BGR2RGB == RGB
 
 
-def _decoded(paths, ahead):
-    """(path, RGB array) in order.  ahead = 0: decoded when asked for; else one thread decodes at most `ahead` images ahead."""
+def _decoded(paths, ahead, keep_format=False):
+    """(path, image array) in order.  ahead = 0: decoded when asked for; else one thread decodes at most `ahead` images ahead."""
     if not ahead:
         for path in paths:
-            yield path, _decode(path)
+            yield path, _decode(path, keep_format)
         return
     import queue
     import threading
@@ -100,7 +117,7 @@ def _decoded(paths, ahead):
             for path in paths:
                 if stop.is_set():
                     return
-                put((path, _decode(path), None))
+                put((path, _decode(path, keep_format), None))
             put(None)
         except BaseException as e:
             put((None, None, e))
@@ -172,24 +189,37 @@ def main(argv=None):
 
 
 def _run(args, model, paths, dev, rank, world, fix, writer, fd, Image):
-    for path, rgb in _decoded(paths, 2 if args.io_threads >= 1 else 0):
-        img_name = os.path.basename(path)
-        xu8 = torch.from_numpy(rgb).to(dev)
-        h, w = rgb.shape[:2]
+    from femasr_amd import channels
+
+    def forward(xu8, fix):
+        """uint8 (H,W,3) -> uint8 (sH,sW,3); None on a rank that does not hold the result."""
+        h, w = xu8.shape[:2]
         if h * w < args.max_size ** 2:
             # whole image: ONE native call, uint8 in -> uint8 out (decode fused into the pad kernel, tensor2img into the crop kernel)
-            u8 = model.test_u8(xu8, **fix) if rank == 0 else None
+            return model.test_u8(xu8, **fix) if rank == 0 else None
+        # tiled: uint8 tiles in, uint8 tiles out - crops, the all-gather over xGMI and the paste move one byte per value, no fp32 image
+        # or canvas is ever held (FeMaSRNet.test_tile_u8); with several ranks only rank 0 pastes
+        if world > 1:
+            return fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend, **fix)
+        return model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend, **fix)
+
+    plain = {k: v for k, v in fix.items() if k != 'color_fix'}              # the alpha plane's forward: everything but the colour fix
+    for path, img in _decoded(paths, 2 if args.io_threads >= 1 else 0, args.keep_format):
+        img_name = os.path.basename(path)
+        xu8 = torch.from_numpy(img).to(dev)
+        if args.keep_format:
+            # the input's channels (femasr_amd.channels): split -> the same forward -> merge; an RGB image is forward(xu8) itself
+            try:
+                u8 = channels.upscale_u8(xu8, lambda x: forward(x, fix), args.out_scale, alpha=args.alpha, run_alpha=lambda x: forward(x, plain))
+            except channels.AlphaTooSmall as e:
+                raise SystemExit(f'{path}: {img.shape[0]}x{img.shape[1]} is too small for the bicubic upscale of its alpha channel ({e}): '
+                                 'pass --alpha network')
         else:
-            # tiled: uint8 tiles in, uint8 tiles out - crops, the all-gather over xGMI and the paste move one byte per value, no fp32 image
-            # or canvas is ever held (FeMaSRNet.test_tile_u8); with several ranks only rank 0 pastes
-            if world > 1:
-                u8 = fd.test_tile_parallel(model, xu8, args.tile_size, args.tile_pad, root_only=True, blend=args.blend, **fix)
-            else:
-                u8 = model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend, **fix)
+            u8 = forward(xu8, fix)
         if writer is not None:
             writer.submit(u8, os.path.join(args.output, img_name))
         elif rank == 0:
-            Image.fromarray(u8.cpu().numpy(), 'RGB').save(os.path.join(args.output, img_name))
+            Image.fromarray(u8.cpu().numpy(), channels.MODES[u8.shape[2] if u8.dim() == 3 else 1]).save(os.path.join(args.output, img_name))
 
 
 if __name__ == '__main__':

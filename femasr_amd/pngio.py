@@ -3,6 +3,7 @@ written behind the forward.  Nothing here changes a pixel: the files decode to e
 
     filter_rows(img, filter='adaptive')           the DEFINITION (numpy, integers only) of the filtered scanlines
     filter_rows_gpu(u8, filter='adaptive')        the same bytes from ONE femasr_png_filter_rgb8 launch (csrc/png_filter.hip)
+    filter_image(img) / filter_image_gpu(u8)      both for any pixel size: (H,W) gray, (H,W,2) gray + alpha, (H,W,3), (H,W,4) RGBA
     encode_png(rows, width, height, level, pool)  filtered scanlines -> the bytes of a PNG file (write_png: the same into a file object)
     adler32_combine(a1, a2, len2)                 the Adler-32 of a concatenation from the Adler-32 of its parts
     PngWriter(threads=8, depth=3)                 submit(u8_cuda, path): filter + D2H on the current stream, encode + write on threads
@@ -34,6 +35,7 @@ ADAPTIVE = 5
 _ADLER_MOD = 65521
 _SIGNATURE = b'\x89PNG\r\n\x1a\n'
 _FILTERS = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': ADAPTIVE}
+CHANNELS = {1: (0, 'L'), 2: (4, 'LA'), 3: (2, 'RGB'), 4: (6, 'RGBA')}      # channels -> (IHDR colour type at bit depth 8, PIL's mode)
 
 
 def filter_code(filter):
@@ -51,15 +53,29 @@ def filter_rows(img, filter='adaptive'):
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
         raise ValueError(f'filter_rows: expected a uint8 (H,W,3) image, got {img.dtype} {img.shape}')
+    return _filter(img, 3, code)
+
+
+def filter_image(img, filter='adaptive'):
+    """The definition for any pixel size: uint8 (H,W) or (H,W,C), C in 1..4 -> uint8 (H, 1 + CW), with C in place of the 3 of the module
+    docstring (the left neighbour of byte i is byte i - C).  C = 3: filter_rows."""
+    code = filter_code(filter)
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in CHANNELS) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f'filter_image: expected a uint8 (H,W) or (H,W,C) image with C in 1..4, got {img.dtype} {img.shape}')
+    return _filter(img, 1 if img.ndim == 2 else img.shape[2], code)
+
+
+def _filter(img, bpp, code):
     H, W = img.shape[:2]
-    n = 3 * W
+    n = bpp * W
     x = img.reshape(H, n).astype(np.int32)
     a = np.zeros_like(x)
-    a[:, 3:] = x[:, :-3]
+    a[:, bpp:] = x[:, :-bpp]
     b = np.zeros_like(x)
     b[1:] = x[:-1]
     c = np.zeros_like(x)
-    c[1:, 3:] = x[:-1, :-3]
+    c[1:, bpp:] = x[:-1, :-bpp]
 
     def residual(t):
         if t == 0:
@@ -115,6 +131,30 @@ def filter_rows_gpu(u8, filter='adaptive', out=None):
     return out
 
 
+def filter_image_gpu(u8, filter='adaptive', out=None):
+    """`filter_image` of a uint8 (H,W), (H,W,C) or (B,H,W,C) GPU tensor, C in 1..4: (H, 1 + CW) / (B, H, 1 + CW), ONE femasr_png_filter_u8
+    launch on the current stream.  A batch needs its channel axis: a 3-D tensor is (H,W,C)."""
+    import torch
+    from . import _lib
+    code = filter_code(filter)
+    if (not torch.is_tensor(u8) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() not in (2, 3, 4) or u8.numel() == 0 or
+            (u8.dim() != 2 and u8.shape[-1] not in CHANNELS)):
+        raise ValueError('filter_image_gpu: expected a non-empty uint8 (H,W), (H,W,C) or (B,H,W,C) GPU tensor with C in 1..4')
+    u8 = u8.contiguous()
+    C = 1 if u8.dim() == 2 else u8.shape[-1]
+    lead = tuple(u8.shape) if u8.dim() == 2 else tuple(u8.shape[:-1])
+    B = lead[0] if len(lead) == 3 else 1
+    H, W = lead[-2:]
+    shape = lead[:-1] + (1 + C * W,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=u8.device)
+    elif not torch.is_tensor(out) or out.shape != shape or out.dtype != torch.uint8 or out.device != u8.device or not out.is_contiguous():
+        raise ValueError(f'filter_image_gpu: out= must be a contiguous uint8 tensor of shape {shape} on {u8.device}')
+    with torch.cuda.device(u8.device):
+        _lib.check(_lib.load().femasr_png_filter_u8(torch.cuda.current_stream(u8.device).cuda_stream, _lib.ptr(u8), B, H, W, C, code, _lib.ptr(out)))
+    return out
+
+
 def adler32_combine(adler1, adler2, len2):
     """Adler-32 of s1 + s2 from adler1 = adler32(s1), adler2 = adler32(s2) and len2 = len(s2)."""
     a1, b1 = adler1 & 0xffff, (adler1 >> 16) & 0xffff
@@ -150,19 +190,21 @@ def _band(view, level, first, last):
     return body, zlib.crc32(body, zlib.crc32(b'IDAT')), zlib.adler32(view), len(view)
 
 
-def _pieces(rows, width, height, level, pool):
+def _pieces(rows, width, height, level, pool, channels=3):
     rows = np.asarray(rows)
     if not isinstance(level, int) or isinstance(level, bool) or not 0 <= level <= 9:
         raise ValueError(f'png level must be an integer in 0..9, got {level!r}')
-    if width < 1 or height < 1 or rows.dtype != np.uint8 or rows.shape != (height, 1 + 3 * width) or not rows.flags.c_contiguous:
-        raise ValueError(f'encode_png: rows must be a contiguous uint8 ({height}, {1 + 3 * width}) array, got {rows.dtype} {rows.shape}')
+    if channels not in CHANNELS:
+        raise ValueError(f'encode_png: channels must be 1 (gray), 2 (gray + alpha), 3 (RGB) or 4 (RGBA), got {channels!r}')
+    if width < 1 or height < 1 or rows.dtype != np.uint8 or rows.shape != (height, 1 + channels * width) or not rows.flags.c_contiguous:
+        raise ValueError(f'encode_png: rows must be a contiguous uint8 ({height}, {1 + channels * width}) array, got {rows.dtype} {rows.shape}')
     bands = band_rows(height, rows.shape[1])
     jobs = [(memoryview(rows[y0:y1]).cast('B'), level, k == 0, k == len(bands) - 1) for k, (y0, y1) in enumerate(bands)]
     done = [_band(*j) for j in jobs] if pool is None else list(pool.map(lambda j: _band(*j), jobs))
     adler = 1
     for _, _, ad, n in done:
         adler = adler32_combine(adler, ad, n)
-    yield _SIGNATURE + _chunk(b'IHDR', struct.pack('>IIBBBBB', width, height, 8, 2, 0, 0, 0))
+    yield _SIGNATURE + _chunk(b'IHDR', struct.pack('>IIBBBBB', width, height, 8, CHANNELS[channels][0], 0, 0, 0))
     for k, (body, crc, _, _) in enumerate(done):
         if k == len(done) - 1:
             tail = struct.pack('>I', adler)
@@ -171,16 +213,17 @@ def _pieces(rows, width, height, level, pool):
     yield _chunk(b'IEND', b'')
 
 
-def encode_png(rows, width, height, level=6, pool=None):
-    """The bytes of the PNG file of a filtered stream `rows` (uint8 (height, 1 + 3 width), host memory).  pool: a
-    concurrent.futures executor for the bands (None: this thread); the result does not depend on it."""
-    return b''.join(_pieces(rows, width, height, level, pool))
+def encode_png(rows, width, height, level=6, pool=None, channels=3):
+    """The bytes of the PNG file of a filtered stream `rows` (uint8 (height, 1 + channels width), host memory).  pool: a
+    concurrent.futures executor for the bands (None: this thread); the result does not depend on it.  channels 1, 2, 3, 4: colour type
+    0 (gray), 4 (gray + alpha), 2 (RGB), 6 (RGBA) at bit depth 8."""
+    return b''.join(_pieces(rows, width, height, level, pool, channels))
 
 
-def write_png(fileobj, rows, width, height, level=6, pool=None):
+def write_png(fileobj, rows, width, height, level=6, pool=None, channels=3):
     """`encode_png` written to a file object; returns the number of bytes."""
     n = 0
-    for piece in _pieces(rows, width, height, level, pool):
+    for piece in _pieces(rows, width, height, level, pool, channels):
         fileobj.write(piece)
         n += len(piece)
     return n
@@ -214,7 +257,7 @@ class _PinnedPool:
 
 
 class PngWriter:
-    """Writes uint8 (H,W,3) GPU images to files behind the caller's stream.
+    """Writes uint8 (H,W,3) GPU images - and (H,W) gray, (H,W,2) gray + alpha, (H,W,4) RGBA ones - to files behind the caller's stream.
 
     submit(u8, path), on the current stream and in this order: the filter kernel, a non-blocking copy of its result into a pinned buffer,
     an event - then it returns.  A writer thread waits for the event, deflates the bands on the shared pool of `threads` threads and writes
@@ -252,9 +295,10 @@ class PngWriter:
     def _gpu_stage(self, u8, is_png):
         """(host array, wait(), release()): the part of submit that touches the GPU."""
         import torch
-        if not torch.is_tensor(u8) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 3 or u8.shape[2] != 3 or u8.numel() == 0:
-            raise ValueError('PngWriter.submit: expected a non-empty uint8 (H,W,3) GPU tensor')
-        dev = filter_rows_gpu(u8) if is_png else u8.contiguous()
+        if (not torch.is_tensor(u8) or not u8.is_cuda or u8.dtype != torch.uint8 or u8.numel() == 0 or
+                not (u8.dim() == 2 or (u8.dim() == 3 and u8.shape[2] in (2, 3, 4)))):
+            raise ValueError('PngWriter.submit: expected a non-empty uint8 (H,W,3) GPU tensor, or (H,W), (H,W,2), (H,W,4)')
+        dev = filter_image_gpu(u8) if is_png else u8.contiguous()
         buf = self._pinned.take(dev.numel())
         host = buf[:dev.numel()].view(dev.shape)
         host.copy_(dev, non_blocking=True)
@@ -273,15 +317,15 @@ class PngWriter:
         if err is not None:
             raise err
 
-    def _job(self, path, is_png, width, height, host, wait, release):
+    def _job(self, path, is_png, width, height, channels, host, wait, release):
         try:
             wait()
             if is_png:
                 with open(path, 'wb') as f:
-                    write_png(f, host, width, height, self.level, self._pool)
+                    write_png(f, host, width, height, self.level, self._pool, channels)
             else:
                 from PIL import Image
-                Image.fromarray(host, 'RGB').save(path)
+                Image.fromarray(host, CHANNELS[channels][1]).save(path)
         except BaseException as e:                            # kept for the caller: nothing is dropped silently
             with self._lock:
                 if self._error is None:
@@ -299,12 +343,13 @@ class PngWriter:
         self._slots.acquire()                                 # blocks while `depth` images are in flight
         try:
             height, width = int(u8.shape[0]), int(u8.shape[1])
+            channels = int(u8.shape[2]) if len(u8.shape) == 3 else 1
             host, wait, release = self._stage(u8, is_png)
         except BaseException:
             self._slots.release()
             raise
         self._pending = [f for f in self._pending if not f.done()]
-        self._pending.append(self._writers.submit(self._job, path, is_png, width, height, host, wait, release))
+        self._pending.append(self._writers.submit(self._job, path, is_png, width, height, channels, host, wait, release))
 
     def close(self):
         """Waits for every file; re-raises the first worker exception.  Idempotent."""

@@ -566,6 +566,31 @@ int femasr_dihedral_merge_u8(void *stream, const uint8_t *straight, const uint8_
  * Refused with FEMASR_ERR_INVALID before any launch: a null pointer, B, H or W <= 0, filter outside 0..5, W > 2^22 (offsets and cost sums
  * inside a row are 32-bit), more than 2^31 - 1 rows in all. */
 int femasr_png_filter_rgb8(void *stream, const uint8_t *img, int B, int H, int W, int filter, uint8_t *out);
+/* The same for any 8-bit pixel size: img uint8 (B,H,W,C), C = 1 (gray, colour type 0), 2 (gray + alpha, 4), 3 (RGB, 2), 4 (RGBA, 6) -> out
+ * uint8 (B,H,1 + C W); the left neighbour of byte i is byte i - C and n = C W (femasr_amd.pngio.filter_image).  C = 3 is the entry above, bit
+ * for bit.  Refused as above, with C outside 1..4 and C W > 3 * 2^22 in place of the limit on W. */
+int
+femasr_png_filter_u8(void *stream, const uint8_t *img, int B, int H, int W, int C, int filter, uint8_t *out);
+
+/* ---- gray, gray + alpha and RGBA images around the 3-channel network (opt-in, femasr_amd.channels) ----
+ * split: img uint8 (B,H,W,C), C = 1, 2, 4 -> rgb uint8 (B,H,W,3) (gray replicated) and, for C = 2, 4, alpha uint8 (B,H,W) (the last channel);
+ *   `alpha` is given exactly when C is 2 or 4.
+ * merge: the final interleaved image out uint8 (s H, s W, channels) from rgb, the network's uint8 (s H, s W, 3) result, and ONE alpha source:
+ *     alpha_lr   uint8 (H,W), the input's alpha plane: out's alpha is rint(clip(imresize(alpha_lr, s), 0, 255)), the bicubic evaluated inside
+ *                the kernel in fp64 from w_h, idx_h (s H, taps_h) and w_w, idx_w (s W, taps_w), the DEVICE tables of the imresize entry for
+ *                scale s without antialiasing: H pass, then W pass, one accumulator per output over its taps in ascending order from 0.0,
+ *                no fma - the byte femasr_amd.channels.alpha_up_ref gives;
+ *     alpha_rgb  uint8 (s H, s W, 3), the network's result for the alpha plane: out's alpha is its gray;
+ *   gray = (19595 R + 38470 G + 7471 B + 32768) >> 16.  channels 1: gray(rgb), no alpha source; 2: gray(rgb), alpha; 4: rgb, alpha.
+ *   channels 1 with rgb == NULL and alpha_lr: the bicubic alpha alone, (s H, s W).  The tables are read only with alpha_lr.
+ * No buffer of a call may overlap another; none needs any alignment.  One launch each on `stream`; no workspace (no plane of the output's
+ * size other than `out` exists), no atomics, no allocation, no synchronisation (capture-safe); 64-bit offsets between rows and images.
+ * Refused with FEMASR_ERR_INVALID before any launch: a missing or surplus pointer, C / channels outside {1, 2, 4}, a count or size <= 0,
+ * s H or s W reaching 2^31, more than 2^31 - 1 blocks of 1024 pixels. */
+int femasr_channels_split_u8(void *stream, const uint8_t *img, int B, int H, int W, int C, uint8_t *rgb, uint8_t *alpha);
+int femasr_channels_merge_u8(void *stream, const uint8_t *rgb, const uint8_t *alpha_lr, const uint8_t *alpha_rgb, int H, int W, int s,
+                             int channels, const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w,
+                             int taps_w, uint8_t *out);
 
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
