@@ -94,6 +94,8 @@ def math_eval(which, x):
 def pad_nchw_to_nhwc(x, hp, wp):
     x = _c(x)
     b, c, h, w = x.shape
+    if not (h <= hp <= 2 * h and w <= wp <= 2 * w):         # (a mirror pad holds at most 2 h rows; femasr_pad_nchw_to_nhwc refuses the same)
+        raise ValueError(f'pad_nchw_to_nhwc: {h}x{w} cannot be mirror-padded to {hp}x{wp}')
     out = np.empty((b, hp, wp, c), np.float32)
     lib().orc_pad_nchw_to_nhwc(_p(x), b, c, h, w, hp, wp, _p(out))
     return out
