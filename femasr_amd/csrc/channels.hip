@@ -30,7 +30,6 @@ constexpr int CH_COLS = CH_TILE + 8;                 // LR columns a block's pix
 enum { CH_ALPHA_NONE = 0, CH_ALPHA_BICUBIC = 1, CH_ALPHA_NETWORK = 2 };
 
 __device__ __forceinline__ bool ch_aligned(const void *p, unsigned a) { return ((uintptr_t)p & (uintptr_t)(a - 1u)) == 0; }
-__device__ __forceinline__ int ch_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ uint32_t ch_gray(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16; }
 // byte e of a little-endian dword array
 template <int N>
@@ -113,7 +112,7 @@ __device__ __forceinline__ double ch_hpass(const uint8_t *__restrict__ a, int H,
 {
     double acc = 0.0;
     for (int k = 0; k < Ph; ++k) {
-        const int j = ch_clamp(idx_h[(size_t)Y * Ph + k], 0, H - 1);      // (tables from imresize_tables are in range; the clamp keeps a bad table in bounds)
+        const int j = clampi(idx_h[(size_t)Y * Ph + k], 0, H - 1);      // (tables from imresize_tables are in range; the clamp keeps a bad table in bounds)
         acc = acc + w_h[(size_t)Y * Ph + k] * (double)a[(size_t)j * W + x];
     }
     return acc;
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(CH_THREADS) void channels_merge_kernel(const uint8_
                 const size_t t0 = (size_t)(X + i) * Pw;
                 double acc = 0.0;
                 for (int k = 0; k < Pw; ++k) {
-                    const int xi = ch_clamp(idx_w[t0 + k], 0, W - 1);
+                    const int xi = clampi(idx_w[t0 + k], 0, W - 1);
                     const double v = (xi >= c0 && xi < c0 + nc) ? col[xi - c0] : ch_hpass(alpha_lr, H, W, Y, xi, w_h, idx_h, Ph);
                     acc = acc + w_w[t0 + k] * v;
                 }

@@ -17,6 +17,7 @@
 // so tests/colorfix_ref.py (float32 numpy) reproduces every bit.  No atomics, no LDS, no scratch; every output element is written by one
 // thread and depends on its own plane only: run-to-run deterministic, independent of batch, grouping and stream.
 #include "common.h"
+#include "pixel.h"
 #include <math.h>
 
 namespace {
@@ -24,8 +25,6 @@ namespace {
 constexpr int CF_THREADS = 256;
 constexpr int CF_MAX_GROUP = 65535;       // planes per launch: grid.y
 constexpr int CF_MAX_LEVELS = 12;
-
-__device__ __forceinline__ int cf_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Element p of plane `unit` of an image batch: fp32 planes back to back, or channel unit % 3 of the uint8 HWC image unit / 3 as
 // (float)byte / 255.0f (IEEE division) - the deinterleave of the uint8 form
@@ -42,7 +41,7 @@ template <bool U8>
 __device__ __forceinline__ float cf_load(const void *base, size_t unit, size_t plane, size_t p)
 {
     if constexpr (U8)
-        return (float)((const uint8_t *)base)[cf_index<U8>(unit, plane, p)] / 255.0f;
+        return pixel_byte_to_unit(((const uint8_t *)base)[cf_index<U8>(unit, plane, p)]);
     else
         return ((const float *)base)[cf_index<U8>(unit, plane, p)];
 }
@@ -59,7 +58,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_hpass_kernel(const void *__rest
     const int i = p / W, x = p - i * W;
     double acc = 0.0;
     for (int k = 0; k < P; ++k) {
-        const int j = cf_clamp(idx[i * P + k], 0, H - 1);      // (tables from imresize_tables are in range; the clamp keeps a bad table in bounds)
+        const int j = clampi(idx[i * P + k], 0, H - 1);      // (tables from imresize_tables are in range; the clamp keeps a bad table in bounds)
         acc = acc + w[i * P + k] * (double)cf_load<U8>(lq, unit, (size_t)H * W, (size_t)j * W + x);
     }
     tmp[blockIdx.y * ((size_t)sH * W) + p] = acc;
@@ -79,7 +78,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_diff_kernel(const double *__res
     const double *src = tmp + blockIdx.y * ((size_t)sH * W) + (size_t)y * W;
     double acc = 0.0;
     for (int k = 0; k < P; ++k) {
-        const int x = cf_clamp(idx[j * P + k], 0, W - 1);
+        const int x = clampi(idx[j * P + k], 0, W - 1);
         acc = acc + w[j * P + k] * src[x];
     }
     d[blockIdx.y * plane + p] = (float)acc - cf_load<U8>(sr, unit, plane, (size_t)p);
@@ -117,13 +116,10 @@ __global__ __launch_bounds__(CF_THREADS) void cf_store_kernel(const void *sr, si
     if (p >= sH * sW) return;
     const size_t plane = (size_t)sH * sW;
     const float v = cf_load<U8>(sr, unit, plane, (size_t)p) + d[blockIdx.y * plane + p];
-    if constexpr (U8) {
-        float q = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-        if (!(q == q)) q = 0.f;
-        ((uint8_t *)out)[cf_index<U8>(unit, plane, p)] = (uint8_t)rintf(q * 255.0f);
-    } else {
+    if constexpr (U8)
+        ((uint8_t *)out)[cf_index<U8>(unit, plane, p)] = pixel_unit_to_byte(v);
+    else
         ((float *)out)[cf_index<U8>(unit, plane, p)] = v;
-    }
 }
 
 size_t cf_align(size_t v) { return (v + 255) & ~(size_t)255; }

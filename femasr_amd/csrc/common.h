@@ -34,12 +34,18 @@ inline int femasr_allow_dynamic_lds(const void *kern, unsigned long long *devs, 
 }
 #define FEMASR_CHECK(expr) do { const int _rc = (expr); if (_rc != FEMASR_OK) return _rc; } while (0)
 
-// blocks of 256 threads for a grid-stride weight repack of `total` items: at most 4096, at least one
-inline unsigned repack_grid(size_t total)
+// blocks of 256 threads for a grid-stride kernel over `total` items (relayouts, tile copies, weight repacks): at most 4096, at least one
+inline unsigned grid_for(size_t total)
 {
     const size_t g = (total + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
+
+// device helpers that more than one translation unit uses
+namespace {
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+}  // namespace
 
 // conv launcher with the VQ-argmin epilogue option (kernels_conv.hip)
 //   vq_part != nullptr : instead of storing the tile, each block writes, per row, the
@@ -127,7 +133,7 @@ enum ConvForm {
     CONV_FORM_COUNT
 };
 
-// Everything the library knows about a form, one row each in kConvForms (kernels_misc.hip): a new form is an enum value, a row, its kernel
+// Everything the library knows about a form, one row each in kConvForms (conv_forms.hip): a new form is an enum value, a row, its kernel
 // file and its place in conv_form()'s precedence (model.hip).
 struct ConvFormDesc {
     ConvForm form;      // the row's own index (femasr_create asserts it)

@@ -23,8 +23,6 @@ struct ConvParams {
 constexpr int BK = 32;
 constexpr int ALD = BK + 1;
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 // Uniform base (SGPR pair) + 32-bit unsigned per-lane BYTE offset: the global_load/store "saddr + voffset" form.  The
 // readfirstlane on both halves pins the (truly uniform) pointer into SGPRs and stops LLVM re-associating
 // (base + lane offset) + uniform offset into per-element 64-bit VALU adds (which then stay live across batched loads).

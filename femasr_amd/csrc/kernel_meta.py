@@ -230,16 +230,23 @@ def code_of(csrc, objs=None):
 
 
 def diff(here, there, rename=()):
-    """One line per kernel of the objects present in both builds: (object, symbol here or there, 'same' | 'differs' | 'only here' |
-    'only there').  rename: (symbol there, symbol here) pairs of kernels whose signature changed."""
+    """One line per kernel: (object, symbol here or there, 'same' | 'differs' | 'only here' | 'only there').  A kernel without a partner in
+    its own object (the object may exist in one build only) is compared with the one unmatched kernel of that symbol in another object of
+    the other build, if there is exactly one, and its line names both: 'object here < object there'.  rename: (symbol there, symbol here)
+    pairs of kernels whose signature changed."""
     ren = dict(rename)
-    lines = []
-    for f in sorted(set(here) & set(there)):
-        old = {ren.get(n, n): v for n, v in there[f].items()}
-        for n in sorted(set(here[f]) | set(old)):
-            what = 'only here' if n not in old else 'only there' if n not in here[f] else 'same' if here[f][n] == old[n] else 'differs'
-            lines.append((f, n, what))
-    return lines
+    old = {f: {ren.get(n, n): v for n, v in ks.items()} for f, ks in there.items()}
+    lines = [(f, n, 'same' if v == old[f][n] else 'differs') for f, ks in here.items() for n, v in ks.items() if n in old.get(f, {})]
+    lone_here = [(f, n) for f, ks in here.items() for n in ks if n not in old.get(f, {})]
+    lone_there = [(g, n) for g, ks in old.items() for n in ks if n not in here.get(g, {})]
+    for f, n in lone_here:
+        homes = [g for g, m in lone_there if m == n]
+        if len(homes) == 1:
+            lone_there.remove((homes[0], n))
+            lines.append((f + ' < ' + homes[0], n, 'same' if here[f][n] == old[homes[0]][n] else 'differs'))
+        else:
+            lines.append((f, n, 'only here'))
+    return sorted(lines + [(g, n, 'only there') for g, n in lone_there])
 
 
 LOOP_PREFIXES = VMEM_PREFIXES + ('ds_', 'v_mfma', 's_waitcnt', 's_barrier')
@@ -273,7 +280,9 @@ if __name__ == '__main__':
             print('%-24s %-10s %s' % (f, what, n))
             if what == 'differs':
                 o = was.get(n, n)
-                print('\n'.join(detail(here[f][n], there[f][o], disassemble(os.path.join(HERE, f))[n], disassemble(os.path.join(other, f))[o])))
+                f, _, g = f.partition(' < ')          # (a kernel that moved: object here < object there)
+                g = g or f
+                print('\n'.join(detail(here[f][n], there[g][o], disassemble(os.path.join(HERE, f))[n], disassemble(os.path.join(other, g))[o])))
         print({w: sum(1 for l in lines if l[2] == w) for w in ('same', 'differs', 'only here', 'only there')})
         sys.exit(1 if any(l[2] == 'differs' for l in lines) else 0)
     rows, bad = check(verbose='--quiet' not in sys.argv)

@@ -829,6 +829,91 @@ int pick_variant(const femasr_conv_args *a, int Ho, int Wo)
     return cls * 2 + a->prologue;
 }
 
+// =================================================================================================================
+// the direct form's weight images
+// =================================================================================================================
+// OIHW -> the FRAGMENT-MAJOR weight layout the conv kernels read straight into MFMA B operands:
+//   out[q][ntile][lane][kk],  q = k/32, kk = (k%32)/2, lane = (k&1)*32 + n%32, ntile = n/32,  zero padded
+//   K order:  I % 32 == 0:  k = ((ci/32)*kh*kw + y*kw + x)*32 + ci%32      (channel blocks outermost)
+//             otherwise  :  k = (y*kw + x)*I + ci
+// thread per OUTPUT element (coalesced stores)
+__global__ void repack_oihw_kernel(const float *__restrict__ in, int O, int I, int kh, int kw, float *__restrict__ out,
+                                   size_t total)
+{
+    const bool blocked = (I % 32) == 0;
+    const int K = I * kh * kw, NT32 = (O + 31) / 32;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int kk = (int)(i & 15), lane = (int)((i >> 4) & 63);
+        const size_t rest = i >> 10;
+        const int ntile = (int)(rest % NT32), q = (int)(rest / NT32);
+        const int k = q * 32 + kk * 2 + (lane >> 5), o = ntile * 32 + (lane & 31);
+        float v = 0.f;
+        if (k < K && o < O) {
+            int ci, x, y;
+            if (blocked) {
+                const int cl = k % 32;
+                int r = k / 32;
+                x = r % kw;
+                r /= kw;
+                y = r % kh;
+                ci = (r / kh) * 32 + cl;
+            } else {
+                ci = k % I;
+                const int r = k / I;
+                x = r % kw;
+                y = r / kw;
+            }
+            v = in[(((size_t)o * I + ci) * kh + y) * kw + x];
+        }
+        out[i] = v;
+    }
+}
+
+// 3x3 OIHW -> the 4 phase matrices of nearest-x2 + conv (oracle/femasr_oracle.c orc_conv_up2_phases): phase (a, b), slot
+// (ty, tx) holds sum over ky in slot ty (ascending) of (sum over kx in slot tx (ascending) of w[o][ci][ky][kx]), slots
+// a=0: {0},{1,2}; a=1: {0,1},{2}.  Each matrix in the fragment-major layout of a 2x2 conv (k = (cb*4 + ty*2 + tx)*32 + ci%32).
+__global__ void repack_up2_kernel(const float *__restrict__ in, int O, int I, float *__restrict__ out, size_t per_phase)
+{
+    const int K = I * 4, NT32 = (O + 31) / 32;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < 4 * per_phase; i += (size_t)gridDim.x * blockDim.x) {
+        const int ph = (int)(i / per_phase);
+        const size_t e = i - (size_t)ph * per_phase;
+        const int kk = (int)(e & 15), lane = (int)((e >> 4) & 63);
+        const size_t rest = e >> 10;
+        const int ntile = (int)(rest % NT32), q = (int)(rest / NT32);
+        const int k = q * 32 + kk * 2 + (lane >> 5), o = ntile * 32 + (lane & 31);
+        float v = 0.f;
+        if (k < K && o < O) {
+            const int a = ph >> 1, b = ph & 1;
+            const int cl = k % 32, r = k / 32, tap = r & 3, ci = (r >> 2) * 32 + cl;
+            const int ty = tap >> 1, tx = tap & 1;
+            const int y0 = ty == 0 ? 0 : (a == 0 ? 1 : 2), y1 = ty == 0 ? (a == 0 ? 0 : 1) : 2;
+            const int x0 = tx == 0 ? 0 : (b == 0 ? 1 : 2), x1 = tx == 0 ? (b == 0 ? 0 : 1) : 2;
+            const float *w = in + ((size_t)o * I + ci) * 9;
+            for (int ky = y0; ky <= y1; ++ky) {
+                float row = w[ky * 3 + x0];
+                for (int kx = x0 + 1; kx <= x1; ++kx) row = row + w[ky * 3 + kx];
+                v = ky == y0 ? row : v + row;
+            }
+        }
+        out[i] = v;
+    }
+}
+
+// compact [k][4] weights of a conv with <= 4 output channels, k in the blocked order above (zero padded to 4 columns)
+__global__ void repack_compact_kernel(const float *__restrict__ in, int O, int I, int kh, int kw, float *__restrict__ out, size_t total)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int o = (int)(i & 3), k = (int)(i >> 2);
+        const int cl = k % 32;
+        int r = k / 32;
+        const int x = r % kw;
+        r /= kw;
+        const int y = r % kh, ci = (r / kh) * 32 + cl;
+        out[i] = o < O ? in[(((size_t)o * I + ci) * kh + y) * kw + x] : 0.f;
+    }
+}
+
 }  // namespace
 
 extern "C" int femasr_conv_small_launch_blocks(int blocks)
@@ -942,3 +1027,44 @@ int femasr_conv2d_launch(hipStream_t s, const femasr_conv_args *a, const conv_vq
     if (flops_out) *flops_out = 2.0 * (double)M * (double)a->Cout * (double)p.K;
     return FEMASR_OK;
 }
+
+extern "C" {
+
+size_t femasr_packed_weight_floats(int O, int I, int kh, int kw)
+{
+    if (O <= 0 || I <= 0 || kh <= 0 || kw <= 0) return 0;
+    const size_t K = (size_t)I * kh * kw;
+    return ((K + 31) / 32) * (size_t)((O + 31) / 32) * 1024 + femasr_compact_weight_floats(O, I, kh, kw);
+}
+
+int femasr_repack_oihw(void *stream, const float *in, int O, int I, int kh, int kw, float *out)
+{
+    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && kh > 0 && kw > 0, "repack: bad args");
+    if (kh == 1 && kw == 1 && (I % 32) == 0) return femasr_repack_k1((hipStream_t)stream, in, O, I, out);   // GEMM layout, same size
+    const size_t tail = femasr_compact_weight_floats(O, I, kh, kw);
+    const size_t total = femasr_packed_weight_floats(O, I, kh, kw) - tail;
+    if (tail) {      // <= 4 output channels (out_conv): compact [k][4] copy behind the fragment-major matrix (direct VALU kernel)
+        hipLaunchKernelGGL(repack_compact_kernel, dim3(grid_for(tail)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw, out + total, tail);
+        FEMASR_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(repack_oihw_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw, out,
+                       total);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
+}
+
+size_t femasr_up2_weight_floats(int O, int I)
+{
+    return (I % 32) == 0 ? 4 * femasr_packed_weight_floats(O, I, 2, 2) : 0;
+}
+
+int femasr_repack_oihw_up2(void *stream, const float *in, int O, int I, float *out)
+{
+    FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 32) == 0, "repack_up2: needs a 3x3 OIHW weight with I %% 32 == 0");
+    const size_t per = femasr_packed_weight_floats(O, I, 2, 2);
+    hipLaunchKernelGGL(repack_up2_kernel, dim3(grid_for(4 * per)), dim3(256), 0, (hipStream_t)stream, in, O, I, out, per);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
+}
+
+}  // extern "C"

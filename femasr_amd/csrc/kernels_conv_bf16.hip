@@ -490,7 +490,7 @@ int femasr_repack_oihw_bf16x3(void *stream, const float *in, int O, int I, int k
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && kh > 0 && kw > 0 && (I % 32) == 0, "repack bf16x3: needs I %% 32 == 0");
     const size_t total = femasr_packed_weight_bf16x3_bytes(O, I, kh, kw) / sizeof(unsigned short);
-    hipLaunchKernelGGL(repack_oihw_bf16x3_kernel, dim3(repack_grid(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw,
+    hipLaunchKernelGGL(repack_oihw_bf16x3_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw,
                        (unsigned short *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;

@@ -349,7 +349,7 @@ int femasr_repack_packed_f16(hipStream_t stream, const float *packed, int O, int
 {
     FEMASR_REQUIRE(packed && out && O > 0 && I > 0 && (I % 32) == 0, "repack f16: needs I %% 32 == 0");
     const size_t total = femasr_packed_weight_f16_bytes(O, I, 3, 3) / sizeof(unsigned short);
-    hipLaunchKernelGGL(repack_f16_kernel<true>, dim3(repack_grid(total)), dim3(256), 0, stream, packed, O, I, 3, 3, (_Float16 *)out, total);
+    hipLaunchKernelGGL(repack_f16_kernel<true>, dim3(grid_for(total)), dim3(256), 0, stream, packed, O, I, 3, 3, (_Float16 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }
@@ -367,7 +367,7 @@ int femasr_repack_oihw_f16(void *stream, const float *in, int O, int I, int kh, 
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && kh > 0 && kw > 0 && (I % 32) == 0, "repack f16: needs I %% 32 == 0");
     const size_t total = femasr_packed_weight_f16_bytes(O, I, kh, kw) / sizeof(unsigned short);
-    hipLaunchKernelGGL(repack_f16_kernel<false>, dim3(repack_grid(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw,
+    hipLaunchKernelGGL(repack_f16_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, kh, kw,
                        (_Float16 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;

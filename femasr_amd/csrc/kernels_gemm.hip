@@ -283,7 +283,7 @@ int femasr_repack_k1(hipStream_t s, const float *in, int O, int I, float *out)
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 32) == 0, "repack_k1: bad args");
     const size_t total = (size_t)I * ((O + 31) / 32) * 32;
-    hipLaunchKernelGGL(repack_k1_kernel, dim3(repack_grid(total)), dim3(256), 0, s, in, O, I, out, total);
+    hipLaunchKernelGGL(repack_k1_kernel, dim3(grid_for(total)), dim3(256), 0, s, in, O, I, out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }

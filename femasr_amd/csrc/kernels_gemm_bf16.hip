@@ -419,7 +419,7 @@ template <class GATHER>
 static int repack_bf16s(void *stream, const float *in, int O, int I, int K, void *out)
 {
     const size_t total = (size_t)(K / 16) * ((O + 31) / 32) * 64;
-    hipLaunchKernelGGL(repack_bf16s_kernel<GATHER>, dim3(repack_grid(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, (uint4 *)out, total);
+    hipLaunchKernelGGL(repack_bf16s_kernel<GATHER>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, O, I, (uint4 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }

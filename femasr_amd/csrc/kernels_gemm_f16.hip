@@ -151,7 +151,7 @@ int repack_k1_f16(hipStream_t s, const float *in, int O, int I, void *out)
 {
     FEMASR_REQUIRE(in && out && O > 0 && I > 0 && (I % 64) == 0, "repack_k1_f16: needs a (out, in) weight with in %% 64 == 0");
     const size_t total = femasr_packed_weight_k1_f16_bytes(O, I) / sizeof(unsigned short);
-    hipLaunchKernelGGL(repack_k1_f16_kernel<PACKED>, dim3(repack_grid(total)), dim3(256), 0, s, in, O, I, (_Float16 *)out, total);
+    hipLaunchKernelGGL(repack_k1_f16_kernel<PACKED>, dim3(grid_for(total)), dim3(256), 0, s, in, O, I, (_Float16 *)out, total);
     FEMASR_CHECK_HIP(hipGetLastError());
     return FEMASR_OK;
 }

@@ -27,6 +27,9 @@
 //
 // Rows whose candidate list overflows (more than VQ_CMAX = 32 entries) are marked VQ_ALL and the exact phase evaluates every code
 // for them: slow, still exact.
+//
+// The single-pass lookup (femasr_vq: row norms, the distance GEMM with its argmin epilogue, vq_finalize_kernel) and the codebook gather
+// stand behind the two-pass kernel.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -48,7 +51,6 @@ constexpr int VQ_STAGE_BUF = 9 * 1024;
 constexpr int VQ_STAGE_BYTES = 8 * 2 * VQ_STAGE_BUF;              // 147 456: covers the bf16 image of the search (<= 131 072)
 __host__ __device__ constexpr size_t vq_fused_list0(int D) { return (size_t)VQ_R * D * 2 > (size_t)VQ_STAGE_BYTES ? (size_t)VQ_R * D * 2 : (size_t)VQ_STAGE_BYTES; }
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ unsigned pack_bf16(float a, float b)
 {
     unsigned r;
@@ -560,6 +562,71 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void vq_candidates_kernel(const Vq
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The single-pass lookup's tail and the helpers around both (femasr_arch.py:35-38,63-66,81-82,95,100,102-112)
+// ------------------------------------------------------------------------------------------
+// |row|^2 as ONE fmaf chain, c ascending; thread per row, float4 loads.
+__global__ void row_sqsum_kernel(const float *__restrict__ x, long long rows, int D, float *__restrict__ out)
+{
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float *p = x + r * D;
+    float acc = 0.f;
+    for (int c = 0; c < D; c += 4) {
+        const float4 v = ld4(p + c);
+        acc = __builtin_fmaf(v.x, v.x, acc);
+        acc = __builtin_fmaf(v.y, v.y, acc);
+        acc = __builtin_fmaf(v.z, v.z, acc);
+        acc = __builtin_fmaf(v.w, v.w, acc);
+    }
+    out[r] = acc;
+}
+
+// one wave per row: pick the first-min over the n-block partials (ascending block order),
+// write idx (int64) and z_q = z + (e[idx] - z).
+__global__ void vq_finalize_kernel(const float *__restrict__ z, long long M, int D, const float *__restrict__ cb,
+                                   const float *__restrict__ part, int nblk, int n_e, long long *__restrict__ idx,
+                                   float *__restrict__ zq)
+{
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int lane = threadIdx.x & 63;
+    const float *pp = part + (size_t)row * nblk * 2;
+    float bd = pp[0];
+    int bi = __float_as_int(pp[1]);
+    for (int b = 1; b < nblk; ++b) {
+        const float d = pp[2 * b];
+        const int i = __float_as_int(pp[2 * b + 1]);
+        if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
+    }
+    bi = bi < 0 ? 0 : (bi >= n_e ? n_e - 1 : bi);     // NaN rows leave the sentinel: never index out of the codebook
+    if (lane == 0) idx[row] = (long long)bi;
+    const float *e = cb + (size_t)bi * D;
+    const float *zr = z + (size_t)row * D;
+    float *o = zq + (size_t)row * D;
+    for (int c = lane * 4; c < D; c += 256) {
+        const float4 zv = ld4(zr + c), ev = ld4(e + c);
+        float4 r;
+        r.x = zv.x + (ev.x - zv.x);
+        r.y = zv.y + (ev.y - zv.y);
+        r.z = zv.z + (ev.z - zv.z);
+        r.w = zv.w + (ev.w - zv.w);
+        *reinterpret_cast<float4 *>(o + c) = r;
+    }
+}
+
+__global__ void codebook_gather_kernel(const long long *__restrict__ idx, long long M, int D, const float *__restrict__ cb,
+                                       int n_e, float *__restrict__ zq)
+{
+    const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int lane = threadIdx.x & 63;
+    long long i = idx[row];
+    i = i < 0 ? 0 : (i >= n_e ? n_e - 1 : i);
+    for (int c = lane * 4; c < D; c += 256)
+        *reinterpret_cast<float4 *>(zq + (size_t)row * D + c) = ld4(cb + (size_t)i * D + c);
+}
+
 constexpr int VQ_NW = 8;
 
 size_t cand_lds_bytes(int n_e, int D, bool fused)
@@ -642,6 +709,50 @@ int femasr_vq_twopass(void *stream, const float *z, int64_t M, int D, const floa
     const float *en = (const float *)((const char *)aux + (size_t)n_e * D * 2);
     VqCandParams p{z, (long long)M, D, n_e, (const uint4 *)aux, ee, en, nullptr, nullptr, cb, (long long *)idx, zq};
     return launch_candidates((hipStream_t)stream, p, true);
+}
+
+// ---- the single-pass lookup (all M x n_e chains on the fp32 MFMA, kernels_gemm.hip with the argmin epilogue) and the helpers
+int femasr_row_sqsum(void *stream, const float *x, int64_t rows, int D, float *out)
+{
+    FEMASR_REQUIRE(x && out && rows > 0 && D > 0 && D % 4 == 0, "row_sqsum: bad args");
+    hipLaunchKernelGGL(row_sqsum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, (hipStream_t)stream, x,
+                       (long long)rows, D, out);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
+}
+
+int femasr_vq(void *stream, const float *z, int64_t M, int D, const float *cb, const float *cbT, const float *ee,
+              int n_e, int64_t *idx, float *zq, void *scratch)
+{
+    FEMASR_REQUIRE(z && cb && cbT && ee && idx && zq && scratch && M > 0, "vq: bad args");
+    FEMASR_REQUIRE(D % 32 == 0 && n_e % 128 == 0, "vq: needs e_dim %% 32 == 0 and n_e %% 128 == 0 (D=%d n_e=%d)", D, n_e);
+    FEMASR_REQUIRE(M < (1ll << 31) - 256, "vq: too many rows");
+    hipStream_t s = (hipStream_t)stream;
+    float *zz = (float *)scratch;
+    float *part = zz + ((M + 63) / 64) * 64;
+    const int nblk = n_e / 128;
+    int rc = femasr_row_sqsum(stream, z, M, D, zz);
+    if (rc) return rc;
+    femasr_conv_args a{};
+    a.in = z; a.B = 1; a.H = (int)M; a.W = 1; a.Cin = D; a.w = cbT; a.bias = nullptr; a.Cout = n_e;
+    a.ksz = 1; a.stride = 1; a.pad = 0; a.up2 = 0; a.prologue = FEMASR_PRO_NONE; a.act = 0;
+    a.Ho = (int)M; a.Wo = 1;
+    conv_vq_epilogue ep{zz, ee, part, nblk};
+    rc = femasr_conv2d_launch(s, &a, &ep, nullptr, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(vq_finalize_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, z, (long long)M, D, cb, part,
+                       nblk, n_e, (long long *)idx, zq);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
+}
+
+int femasr_codebook_gather(void *stream, const int64_t *idx, int64_t M, int D, const float *cb, int n_e, float *zq)
+{
+    FEMASR_REQUIRE(idx && cb && zq && M > 0 && D % 4 == 0 && n_e > 0, "codebook_gather: bad args");
+    hipLaunchKernelGGL(codebook_gather_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long *)idx, (long long)M, D, cb, n_e, zq);
+    FEMASR_CHECK_HIP(hipGetLastError());
+    return FEMASR_OK;
 }
 
 }  // extern "C"

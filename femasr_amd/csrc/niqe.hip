@@ -34,8 +34,6 @@ constexpr int MS_TW = 32, MS_TH = 32;            // MSCN tile: 32 columns (one p
 constexpr int MS_IW = MS_TW + 6, MS_IH = MS_TH + 6;      // staged tile: 38 x 38 fp64 = 11.3 KiB of LDS
 constexpr int NQ_SUMS = 30;                      // per block: 5 maps x (n<0, sum x² | x<0, n>0, sum x² | x>0, sum |x|, sum x²)
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // img: (B,H,W,3); y, yn: (B,Hb,Wb), the top-left Hb x Wb of the cropped image
 __global__ __launch_bounds__(NQ_THREADS) void niqe_y_kernel(const uint8_t *__restrict__ img, int H, int W, int crop, int Hb, int Wb,
                                                             double *__restrict__ y, double *__restrict__ yn)

@@ -81,7 +81,7 @@ def _slot(a):
 
 
 def _gn_tiles(form, a):
-    """The forms' gn_tiles rules (csrc/kernels_misc.hip kConvForms): fused GroupNorm partials per sample of this form, 0 = none."""
+    """The forms' gn_tiles rules (csrc/conv_forms.hip kConvForms): fused GroupNorm partials per sample of this form, 0 = none."""
     c = a.Cout
     fus = c % 32 == 0 and (c // 32) & (c // 32 - 1) == 0 and c // 32 <= 32
     halo = a.ksz == 3 and a.stride == 1 and a.pad == 1 and a.Cin % 32 == 0 and a.act in (0, 2) and not (a.up2 and a.prologue)

@@ -45,6 +45,39 @@ def test_pad_crop_exact(cuda_device):
     assert lib.femasr_pad_nchw_to_nhwc(None, _lib.ptr(tx), 3, 3, 21, 30, 64, 32, _lib.ptr(out)) != 0
 
 
+def test_unit_float_to_byte_rule_at_ties_and_non_finite(cuda_device):
+    """The one float -> byte rule (csrc/pixel.h: clamp to [0,1], NaN -> 0, x255, round half to even) through both kernels that end in it,
+    femasr_crop_nhwc_to_u8hwc (both channel orders) and femasr_image_f32_to_u8: NaN, +-inf, -0.0, values outside [0,1], and for every k in
+    0..254 the fp32 value nearest (k + 0.5)/255 with its two neighbours, where x255 lands on, just below or just above a tie.  These are
+    775 values and a 13x17 RGB image holds 663, so they fill two such images (the rest: uniform in [-0.5, 1.5])."""
+    import gpu_utils as G
+    lib = _lib.load()
+    tie = ((np.arange(255, dtype=np.float64) + 0.5) / 255.0).astype(np.float32)
+    special = np.array([np.nan, np.inf, -np.inf, -0.0, 0.0, -1e-3, -7.0, 1.0, 1.0 + 2.0 ** -23, 3.5], dtype=np.float32)
+    vals = np.concatenate([special, np.nextafter(tie, np.float32(0)), tie, np.nextafter(tie, np.float32(2))])
+    B, H, W = 2, 13, 17
+    v = synth.uniform(2, 'ties', (B * H * W * 3,), -0.5, 1.5).astype(np.float32)
+    v[:vals.size] = vals
+    v = np.random.default_rng(0).permutation(v).reshape(B, H, W, 3)
+    with np.errstate(invalid='ignore'):
+        ref = np.rint(np.where(np.isnan(v), np.float32(0), np.clip(v, np.float32(0), np.float32(1))) * np.float32(255))
+    assert ref.dtype == np.float32
+    ref = ref.astype(np.uint8)
+    assert len(np.unique(ref)) == 256
+    tv = G.dev(v)
+    chw = [G.dev(np.ascontiguousarray(v[b].transpose(2, 0, 1))) for b in range(B)]
+    for swap in (0, 1):
+        want = ref[..., ::-1] if swap else ref
+        crop = torch.empty((B, H, W, 3), dtype=torch.uint8, device='cuda')
+        _lib.check(lib.femasr_crop_nhwc_to_u8hwc(None, _lib.ptr(tv), B, H, W, H, W, swap, _lib.ptr(crop)))
+        _same(crop.cpu().numpy(), want, f'crop_nhwc_to_u8hwc swap {swap}')
+        img = torch.empty((B, H, W, 3), dtype=torch.uint8, device='cuda')
+        for b in range(B):
+            _lib.check(lib.femasr_image_f32_to_u8(None, _lib.ptr(chw[b]), H, W, swap, _lib.ptr(img[b])))
+        _same(img.cpu().numpy(), want, f'image_f32_to_u8 swap {swap}')
+        _same(img.cpu().numpy(), crop.cpu().numpy(), f'image_f32_to_u8 against crop_nhwc_to_u8hwc, swap {swap}')
+
+
 CONV_CASES = [
     # name, (B,H,W,Cin), Cout, k, s, p, up2
     ('in_conv_k4_cin3', (2, 31, 33, 3), 256, 4, 1, 1, False),

@@ -188,30 +188,40 @@ def test_library_reads_one_environment_variable():
 
 def test_kernel_meta_diff_tells_same_from_differs():
     """kernel_meta.py --diff (how a refactor shows that it left the device code alone): an object against itself is `same` kernel by kernel;
-    with one instruction of one kernel changed in memory that kernel, and only that one, `differs`; so does one with another register count."""
+    with one instruction of one kernel changed in memory that kernel, and only that one, `differs`; so does one with another register count.
+    A kernel that moved to another object is found there by its symbol: `same` if unchanged, `differs` with one instruction changed."""
     import sys
     csrc = os.path.join(ROOT, 'femasr_amd', 'csrc')
-    if not os.path.exists(os.path.join(csrc, 'kernels_misc.o')) or not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-objdump'):
+    if not os.path.exists(os.path.join(csrc, 'kernels_layout.o')) or not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-objdump'):
         pytest.skip('no built objects / no llvm-objdump here')
     sys.path.insert(0, csrc)
     import kernel_meta
-    here = kernel_meta.code_of(csrc, objs=['kernels_misc.o'])
-    assert list(here) == ['kernels_misc.o'] and len(here['kernels_misc.o']) >= 29
+    held = {'kernels_attn.o': 1, 'kernels_layout.o': 13, 'kernels_norm.o': 10, 'kernels_probe.o': 1}      # the kernels each object holds
+    here = kernel_meta.code_of(csrc, objs=list(held))
+    assert {f: len(ks) for f, ks in here.items()} == held
     lines = kernel_meta.diff(here, here)
-    assert len(lines) == len(here['kernels_misc.o']) and all(what == 'same' for _, _, what in lines), lines
-    victim, other = sorted(here['kernels_misc.o'])[:2]
-    insts, meta = here['kernels_misc.o'][victim]
+    assert len(lines) == sum(held.values()) and all(what == 'same' for _, _, what in lines), lines
+    layout = here['kernels_layout.o']
+    victim, other = sorted(layout)[:2]
+    insts, meta = layout[victim]
     assert len(insts) > 4
-    doctored = dict(here['kernels_misc.o'])
+    doctored = dict(layout)
     doctored[victim] = (insts[:3] + [('s_nop', '0')] + insts[4:], meta)
     doctored[other] = (doctored[other][0], ('999',) + doctored[other][1][1:])
-    last = sorted(here['kernels_misc.o'])[-1]
+    last = sorted(layout)[-1]
     doctored['old_name'] = doctored.pop(last)          # (a kernel whose signature changed: matched only through --rename)
-    got = {n: what for _, n, what in kernel_meta.diff(here, {'kernels_misc.o': doctored})}
+    there = dict(here, **{'kernels_layout.o': doctored})
+    got = {n: what for _, n, what in kernel_meta.diff(here, there)}
     assert got.pop(victim) == 'differs' and got.pop(other) == 'differs' and got.pop(last) == 'only here' and got.pop('old_name') == 'only there'
-    assert set(got.values()) == {'same'}
-    got = {n: what for _, n, what in kernel_meta.diff(here, {'kernels_misc.o': doctored}, rename=[('old_name', last)])}
+    assert set(got.values()) == {'same'} and len(got) == sum(held.values()) - 3
+    got = {n: what for _, n, what in kernel_meta.diff(here, there, rename=[('old_name', last)])}
     assert got[last] == 'same' and 'old_name' not in got and sorted(got.values()).count('differs') == 2
+    # one kernel moved from a.o to b.o (b.o exists in this build only), unchanged, then with one instruction changed
+    stayed = {n: v for n, v in layout.items() if n != victim}
+    for moved, want in ((layout[victim], 'same'), (doctored[victim], 'differs')):
+        lines = kernel_meta.diff({'a.o': stayed, 'b.o': {victim: moved}}, {'a.o': layout})
+        assert ('b.o < a.o', victim, want) in lines and len(lines) == len(layout), lines
+        assert all(f == 'a.o' and what == 'same' for f, n, what in lines if n != victim), lines
 
 
 def test_kernel_meta_detail_tells_a_moved_loop_instruction():
