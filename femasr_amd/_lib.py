@@ -161,6 +161,7 @@ DEBUG_SIGNATURES = {
     'femasr_conv_small_launch_blocks': (c_int, [c_int]),
     'femasr_debug_conv_variant_name': (c_int, [ctypes.POINTER(ConvArgs), ctypes.c_char_p, c_int]),
     'femasr_debug_weight_image_bytes': (c_int, [vp, c_int, ctypes.POINTER(szt)]),
+    'femasr_debug_math_eval': (c_int, [vp, c_int, vp, ctypes.c_longlong, vp]),
 }
 
 _lib = None

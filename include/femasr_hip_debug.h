@@ -44,6 +44,13 @@ int femasr_debug_conv_variant_name(const femasr_conv_args *a, char *name, int ca
  * phase matrices).  tests/ check with it that an fp16 image exists only once its mode has been selected (tests/test_gpu_weight_images.py). */
 int femasr_debug_weight_image_bytes(const femasr_handle *h, int form, size_t *bytes);
 
+/* The device's elementary functions on their own: y[i] = f(x[i]) for n values.  fn 0-3: det_expf, det_erff, det_silu, det_gelu
+ * (csrc/detmath.h);  4-7: their two-at-a-time forms det_expf2 .. det_gelu2 on the pairs (x[2i], x[2i+1]), n even;  8: fast_silu
+ * (csrc/halo_mma.h, the hardware exp2 / rcp SiLU of the tolerance-based forms).  A bad fn, a null pointer, n <= 0 or an odd n
+ * for a packed form returns FEMASR_ERR_INVALID and writes nothing.  The float2 accesses of the packed forms need x and y 8-byte
+ * aligned.  tests/test_gpu_math_range.py sweeps all of fp32 through it against the oracle (orc_math_eval). */
+int femasr_debug_math_eval(void *stream, int fn, const float *x, long long n, float *y);
+
 #ifdef __cplusplus
 }
 #endif

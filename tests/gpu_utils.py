@@ -223,6 +223,19 @@ def gn_silu_apply(x, a, b):
     return ops.get('y', torch.float32, x.shape).cpu().numpy()
 
 
+MATH_FN = {'exp': 0, 'erf': 1, 'silu': 2, 'gelu': 3, 'exp2': 4, 'erf2': 5, 'silu2': 6, 'gelu2': 7, 'fast_silu': 8}
+
+
+def math_eval(fn, x):
+    """The device's own elementary functions through femasr_debug_math_eval (fn: a key of MATH_FN; the '2' forms take the pairs
+    (x[2i], x[2i+1]))."""
+    x = np.ascontiguousarray(x, np.float32)
+    ops = Operands(f'debug_math_eval {fn} n {x.size}').inp('x', x).out('y', 4 * x.size).build()
+    _lib.check(_lib.load().femasr_debug_math_eval(None, MATH_FN[fn], ops.p('x'), x.size, ops.p('y')))
+    ops.check()
+    return ops.get('y', torch.float32, x.shape).cpu().numpy()
+
+
 def gn_coeffs(x, gamma, beta, eps=1e-6, groups=32):
     lib = _lib.load()
     b, h, w, c = x.shape

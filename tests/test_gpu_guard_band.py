@@ -318,6 +318,48 @@ def test_vq_family(cuda_device, m):
     _same(GA.run_twice(gather, f'codebook_gather M {m}'), cb[idx_ref], f'codebook_gather M {m}')
 
 
+def _math_inputs(n):
+    """n values spread over the whole call-site set (specials, subnormals and both clamps' neighbourhoods at n = 63, 65)."""
+    import math_range as MR
+    s = MR.call_site_set()
+    return np.ascontiguousarray(s[np.linspace(0, s.size - 1, n).astype(np.int64)])
+
+
+@pytest.mark.parametrize('n', [1, 2, 63, 65])
+def test_debug_math_eval(cuda_device, n):
+    """femasr_debug_math_eval: one value (or pair) per thread, grid-stride over blocks of 256.  The scalar selectors at every n, the
+    packed ones (float2 accesses) at the even n."""
+    import math_range as MR
+    x = _math_inputs(n)
+    assert x.size == n
+    for fn, code in G.MATH_FN.items():
+        if fn.endswith('2') and n % 2:
+            continue                    # refused: test_debug_math_eval_refusals
+        what = f'debug_math_eval {fn} n {n}'
+        y = GA.run_twice(lambda: G.math_eval(fn, x), what)
+        if code < 8:
+            MR.assert_same(y, orc.math_eval(fn.rstrip('2'), x), what, x)
+
+
+@pytest.mark.parametrize('n', [1, 2, 63, 65])
+def test_debug_math_eval_refusals(cuda_device, n):
+    """A bad fn, a null pointer, n <= 0 and - for the packed selectors - an odd n return FEMASR_ERR_INVALID and write nothing: y keeps
+    its poison and no guard byte changes."""
+    lib = _lib.load()
+    x = _math_inputs(n)
+    ops = G.Operands(f'debug_math_eval refusals n {n}').inp('x', x).out('y', 4 * n).build()
+    poison = ops.get('y', torch.int32)
+    px, py = ops.p('x'), ops.p('y')
+    calls = [(9, px, n, py), (-1, px, n, py), (0, None, n, py), (0, px, n, None), (4, None, 2, py), (0, px, 0, py), (0, px, -2, py),
+             (7, px, 0, py)]
+    if n % 2:
+        calls += [(code, px, n, py) for code in (4, 5, 6, 7)]
+    for args in calls:
+        assert lib.femasr_debug_math_eval(None, *args) == -1, args          # FEMASR_ERR_INVALID
+    ops.check()
+    assert torch.equal(ops.get('y', torch.int32), poison), 'a refused call wrote to y'
+
+
 # ---------------------------------------------------------------- window attention: one (window, head) per wave, 8 x 8 windows
 @pytest.mark.parametrize('b,h,w', [(1, 8, 8), (2, 8, 8), (1, 16, 16), (2, 16, 16)])
 @pytest.mark.parametrize('shift', [0, 4])

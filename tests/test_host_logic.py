@@ -196,7 +196,7 @@ def test_kernel_meta_diff_tells_same_from_differs():
         pytest.skip('no built objects / no llvm-objdump here')
     sys.path.insert(0, csrc)
     import kernel_meta
-    held = {'kernels_attn.o': 1, 'kernels_layout.o': 13, 'kernels_norm.o': 10, 'kernels_probe.o': 1}      # the kernels each object holds
+    held = {'kernels_attn.o': 1, 'kernels_layout.o': 13, 'kernels_norm.o': 10, 'kernels_probe.o': 2}      # the kernels each object holds
     here = kernel_meta.code_of(csrc, objs=list(held))
     assert {f: len(ks) for f, ks in here.items()} == held
     lines = kernel_meta.diff(here, here)
