@@ -602,6 +602,49 @@ class FeMaSRNet(nn.Module):
         _lib.check(lib.femasr_decode_indices(h, self._stream(dev), _lib.ptr(idx), b, qh, qw, _lib.ptr(out), _lib.ptr(ws), ws.numel()))
         return out
 
+    # ------------------------------------------------------------------ the network as an encoder
+    def _encode_native(self, x, in_u8, bgr, pad_mode):
+        """One `femasr_encode` on the current stream: forward's launch schedule cut behind the last codebook lookup.
+        `x`: contiguous fp32 (B,3,H,W) or uint8 (B,H,W,3).  Returns the index maps, views of one flat tensor."""
+        fmt = _U8 if in_u8 else _FP32
+        lib, h = self._native(x.device)
+        b, _, hh, ww = fmt.bchw(x)
+        _, qhw = self._geometry(lib, h, fmt, b, hh, ww, pad_mode)
+        ws = self._workspace(lib.femasr_encode_workspace_bytes, h, (b, hh, ww, pad_mode), x.device)
+        idx_all = torch.empty((sum(b * a * c for a, c in qhw),), dtype=torch.int64, device=x.device)
+        _lib.check(lib.femasr_encode(h, self._stream(x.device), _lib.ptr(x), int(in_u8), int(bool(bgr)), b, hh, ww, pad_mode,
+                                     _lib.ptr(idx_all), _lib.ptr(ws), ws.numel()))
+        idx, off = [], 0
+        for qh, qw in qhw:
+            idx.append(idx_all[off:off + b * qh * qw].view(b, 1, qh, qw))
+            off += b * qh * qw
+        return idx
+
+    @torch.no_grad()
+    def encode_indices(self, input, pad=False):
+        """Image batch -> the VQ index maps alone, one (B,1,qh,qw) int64 map per codebook: the network as an encoder (the frozen HQ net
+        that makes `gt_indices`, basicsr/models/femasr_model.py:145-146; vis_codebook.py).  pad=False: `forward`'s geometry, the result
+        equals `forward(input)[3]`; pad=True: `test()`'s mirror pad, the result equals `test_with_all_indices(input)[1]` - bit for bit:
+        every launch in front of a lookup is the forward's, and nothing behind the last lookup runs (no after_quant conv, no decoder stage,
+        no out_conv, no image; in LQ nets no encoder up-block that only feeds decoder skips).  `linear_math` and `num_streams` act as in the
+        forward; `decoder_math` cannot change an index and, with one codebook, selects nothing that runs.  Always eager, also with
+        `use_graph = True` (the call is short; it is capture-safe for a caller who captures it by hand: set `_ws = None` around the
+        capture, as `_run` does, so that the graph owns its workspace)."""
+        if input.dim() != 4 or input.shape[1] != self.in_channel:
+            raise ValueError(f'expected (B,{self.in_channel},H,W), got {tuple(input.shape)}')
+        if input.device.type != 'cuda':
+            raise _lib.FemasrError('encode_indices: tensor must be on the GPU (no CPU fallback)')
+        return self._encode_native(input.detach().to(torch.float32).contiguous(), False, False, int(bool(pad)))
+
+    @torch.no_grad()
+    def encode_indices_u8(self, img_u8, bgr=False, pad=True):
+        """`encode_indices` on uint8 (H,W,3) or (B,H,W,3) image(s) on the GPU: the decode (`/255.`, bgr=True: cv2's channel order) is fused
+        into the mirror-pad kernel as in `test_u8`, so the maps are those of `encode_indices(imgproc.u8_to_input(img), pad)`.  Eager."""
+        if img_u8.device.type != 'cuda':
+            raise _lib.FemasrError('encode_indices_u8: tensor must be on the GPU (no CPU fallback)')
+        x, _ = self._u8_batch(img_u8)
+        return self._encode_native(x, True, bgr, int(bool(pad)))
+
     # ------------------------------------------------------------------ tiled inference
     @torch.no_grad()
     def test_tile(self, input, tile_size=240, tile_pad=16, rank=0, world_size=1, gather=None, paste=True, blend=False, color_fix=False,

@@ -8,6 +8,8 @@
 //   SwinLayers / RSTB / SwinTransformerBlock   femasr_arch.py:114-132; network_swinir.py:442-482,239-279
 //   DecoderBlock x3 + out_conv     femasr_arch.py:195-211,267-273,366-369
 //   FeMaSRNet.decode_indices       femasr_arch.py:376-385
+//   the network as an encoder      basicsr/models/femasr_model.py:145-146, vis_codebook.py:36 (femasr_encode: the same schedule, cut
+//                                  behind the last codebook lookup)
 // but on NHWC activations, with every elementwise / normalisation op folded into the
 // neighbouring implicit-GEMM launch (see kernels_conv.hip) — about 300 launches per forward,
 // all on the caller's stream, no host synchronisation.
@@ -203,7 +205,7 @@ struct femasr_handle {
     std::vector<hipStream_t> sub_streams;
     std::vector<hipEvent_t> sub_done;
     hipEvent_t ev_fork = nullptr;
-    std::map<std::array<int, 4>, std::vector<size_t>> plans;      // workspace plans per (B, H, W, pad_mode)
+    std::map<std::array<int, 5>, std::vector<size_t>> plans;      // workspace plans per (B, H, W, pad_mode, encode only)
 };
 
 namespace {
@@ -437,6 +439,7 @@ struct Ctx {
     int rc = 0;
     // femasr_forward_u8: the first / last kernel of the forward read / write uint8 HWC images directly (bit 0: input, bit 1: output)
     int io_u8 = 0, swap_rb = 0;
+    bool encode_only = false;       // femasr_encode: the schedule ends behind the lookup of the last codebook scale (run_tail)
     bool dry() const { return arena->dry; }
     hipStream_t s() const { return stream; }
 
@@ -747,6 +750,13 @@ int run_tail(Ctx &c, T x, std::vector<T> &feats, bool fuse_skip, bool with_encod
             }
             if (idx_tmp) c.release(idx_tmp);
             ++nq_done;
+            if (c.encode_only && i == h->last_quant_stage) {        // femasr_encode: the last index map is written; nothing behind it runs
+                c.release(z);
+                c.release(zq);
+                if (prev_q.p) c.release(prev_q);
+                if (pending_add.p) c.release(pending_add);
+                return c.rc;
+            }
             T qv = cfg.use_quantize ? zq : z;
             c.release(cfg.use_quantize ? z : zq);
             T ain = qv;
@@ -795,16 +805,17 @@ int run_tail(Ctx &c, T x, std::vector<T> &feats, bool fuse_skip, bool with_encod
 }
 
 int run_forward(femasr_handle *h, Arena *arena, hipStream_t stream, const float *in_nchw, int B, int H, int W, int pad_mode,
-                float *out_nchw, int64_t *const *idx_out, int io_u8 = 0, int swap_rb = 0)
+                float *out_nchw, int64_t *const *idx_out, int io_u8 = 0, int swap_rb = 0, bool encode_only = false)
 {
     const femasr_config &cfg = h->cfg;
     Ctx c{h, arena, stream};
-    c.io_u8 = io_u8; c.swap_rb = swap_rb;
+    c.io_u8 = io_u8; c.swap_rb = swap_rb; c.encode_only = encode_only;
     Geometry g;
     int rc = plan_geometry(h, H, W, pad_mode, &g);
     if (rc) return rc;
     const bool fuse_skip = cfg.lq_stage && cfg.use_residual;
-    auto needed = [&](int i) {        // is enc_feats[i] read by the decoder side?
+    auto needed = [&](int i) {        // is enc_feats[i] read by the decoder side?  (femasr_encode: by what runs up to the last lookup)
+        if (encode_only && i > h->last_quant_stage) return false;
         return i == 0 || quant_at(h, i, nullptr) || fuse_skip;
     };
 
@@ -1047,10 +1058,12 @@ static void sub_range(int B, int S, int i, int *lo, int *hi)
 }
 
 // Workspace plan of one call shape: per sub-batch arena peaks (a dry run of the launch schedule), cached per
-// (B, H, W, pad_mode) until the stream count / decoder math / weights change.
-static int plan_for(femasr_handle *h, int B, int H, int W, int pad_mode, const std::vector<size_t> **out)
+// (B, H, W, pad_mode, encode only) until the stream count / decoder math / weights change.  The plan of femasr_encode has a key of its own:
+// its schedule is shorter and holds fewer features, and its index maps are never workspace (the caller's buffer is required).
+static int plan_for(femasr_handle *h, int B, int H, int W, int pad_mode, bool encode_only, const std::vector<size_t> **out)
 {
-    const std::array<int, 4> key{B, H, W, pad_mode};
+    const std::array<int, 5> key{B, H, W, pad_mode, encode_only ? 1 : 0};
+    int64_t *const idx_dry[FEMASR_MAX_CODEBOOKS] = {(int64_t *)4096, (int64_t *)4096, (int64_t *)4096};      // dry run: never dereferenced
     auto it = h->plans.find(key);
     if (it == h->plans.end()) {
         const int S = std::min(h->nsub, B);
@@ -1060,7 +1073,7 @@ static int plan_for(femasr_handle *h, int B, int H, int W, int pad_mode, const s
             sub_range(B, S, i, &lo, &hi);
             Arena a;
             a.reset(nullptr, 0, true);
-            const int rc = run_forward(h, &a, nullptr, nullptr, hi - lo, H, W, pad_mode, nullptr, nullptr);
+            const int rc = run_forward(h, &a, nullptr, nullptr, hi - lo, H, W, pad_mode, nullptr, encode_only ? idx_dry : nullptr, 0, 0, encode_only);
             if (rc) return rc;
             need.push_back((a.peak + 255) & ~(size_t)255);
         }
@@ -1076,11 +1089,24 @@ int femasr_workspace_bytes(const femasr_handle *hc, int B, int H, int W, int pad
     femasr_handle *h = const_cast<femasr_handle *>(hc);
     FEMASR_REQUIRE(h && bytes && B > 0 && H > 0 && W > 0, "workspace_bytes: bad args");
     const std::vector<size_t> *need = nullptr;
-    const int rc = plan_for(h, B, H, W, pad_mode, &need);
+    const int rc = plan_for(h, B, H, W, pad_mode, false, &need);
     if (rc) return rc;
     size_t total = 0;
     for (size_t n : *need) total += n;
     *bytes = total + 256;
+    return FEMASR_OK;
+}
+
+int femasr_encode_workspace_bytes(const femasr_handle *hc, int B, int H, int W, int pad_mode, size_t *bytes)
+{
+    femasr_handle *h = const_cast<femasr_handle *>(hc);
+    FEMASR_REQUIRE(h && bytes && B > 0 && H > 0 && W > 0, "encode_workspace_bytes: bad args");
+    const std::vector<size_t> *need = nullptr;
+    const int rc = plan_for(h, B, H, W, pad_mode, true, &need);
+    if (rc) return rc;
+    size_t total = 0;
+    for (size_t n : *need) total += n;
+    *bytes = total;         // exact: femasr_encode refuses anything smaller before its first launch
     return FEMASR_OK;
 }
 
@@ -1120,12 +1146,14 @@ int femasr_set_streams(femasr_handle *h, int n)
     return FEMASR_OK;
 }
 
+// encode_only (femasr_encode): no image (out_nchw is null), `indices` required, the workspace checked against the plan up front
 static int forward_impl(femasr_handle *h, void *stream, const float *in_nchw, int B, int H, int W, int pad_mode,
-                        float *out_nchw, int64_t *indices, void *ws, size_t ws_bytes, int io_u8, int swap_rb)
+                        float *out_nchw, int64_t *indices, void *ws, size_t ws_bytes, int io_u8, int swap_rb, bool encode_only = false)
 {
     int rc = check_ready(h);
     if (rc) return rc;
-    FEMASR_REQUIRE(in_nchw && out_nchw && ws && B > 0 && H > 0 && W > 0, "forward: bad args");
+    FEMASR_REQUIRE(in_nchw && (encode_only ? indices != nullptr : out_nchw != nullptr) && ws && B > 0 && H > 0 && W > 0,
+                   encode_only ? "encode: bad args" : "forward: bad args");
     FEMASR_REQUIRE(!io_u8 || h->cfg.in_channel == 3, "forward_u8: 3-channel images only");
     FEMASR_REQUIRE(((uintptr_t)ws & 255) == 0, "forward: workspace must be 256-byte aligned");
     DeviceGuard guard(h->cfg.device);
@@ -1146,13 +1174,18 @@ static int forward_impl(femasr_handle *h, void *stream, const float *in_nchw, in
         }
     }
     const std::vector<size_t> *need = nullptr;
-    rc = plan_for(h, B, H, W, pad_mode, &need);
+    rc = plan_for(h, B, H, W, pad_mode, encode_only, &need);
     if (rc) return rc;
     const int S = (int)need->size();
+    if (encode_only) {
+        size_t total = 0;
+        for (size_t n : *need) total += n;
+        if (total > ws_bytes) return femasr_set_error(FEMASR_ERR_WORKSPACE, "encode: workspace of %zu bytes, %zu needed (femasr_encode_workspace_bytes)", ws_bytes, total);
+    }
     if (S <= 1) {
         Arena a;
         a.reset(ws, ws_bytes, false);
-        return run_forward(h, &a, caller, in_nchw, B, H, W, pad_mode, out_nchw, indices ? qbase : nullptr, io_u8, swap_rb);
+        return run_forward(h, &a, caller, in_nchw, B, H, W, pad_mode, out_nchw, indices ? qbase : nullptr, io_u8, swap_rb, encode_only);
     }
     // fork: every sub-batch stream waits for the caller's stream; join: the caller's stream waits for all of them.
     // Only event dependencies are added — no host synchronisation.
@@ -1176,7 +1209,8 @@ static int forward_impl(femasr_handle *h, void *stream, const float *in_nchw, in
         int64_t *qsub[FEMASR_MAX_CODEBOOKS];
         for (int q = 0; q < FEMASR_MAX_CODEBOOKS; ++q) qsub[q] = qbase[q] ? qbase[q] + lo * qstride[q] : nullptr;
         rc = run_forward(h, &a, st, (const float *)((const char *)in_nchw + lo * in_stride), hi - lo, H, W, pad_mode,
-                         (float *)((char *)out_nchw + lo * out_stride), indices ? qsub : nullptr, io_u8, swap_rb);
+                         out_nchw ? (float *)((char *)out_nchw + lo * out_stride) : nullptr, indices ? qsub : nullptr, io_u8, swap_rb,
+                         encode_only);
     }
     // join every stream that was forked - also on an error, so that nothing still runs on ws / out when the caller's
     // stream continues
@@ -1198,6 +1232,13 @@ int femasr_forward_u8(femasr_handle *h, void *stream, const uint8_t *in_hwc, int
                       uint8_t *out_hwc, int64_t *indices, void *ws, size_t ws_bytes)
 {
     return forward_impl(h, stream, (const float *)in_hwc, B, H, W, pad_mode, (float *)out_hwc, indices, ws, ws_bytes, 3, swap_rb ? 1 : 0);
+}
+
+int femasr_encode(femasr_handle *h, void *stream, const void *in, int in_u8, int swap_rb, int B, int H, int W, int pad_mode,
+                  int64_t *indices, void *ws, size_t ws_bytes)
+{
+    return forward_impl(h, stream, (const float *)in, B, H, W, pad_mode, nullptr, indices, ws, ws_bytes, in_u8 ? 1 : 0,
+                        (in_u8 && swap_rb) ? 1 : 0, true);
 }
 
 int femasr_decode_workspace_bytes(const femasr_handle *hc, int B, int hq, int wq, size_t *bytes)

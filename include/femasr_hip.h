@@ -124,6 +124,10 @@ int femasr_decode_workspace_bytes(const femasr_handle *h, int B, int hq, int wq,
 int femasr_decode_indices(femasr_handle *h, void *stream, const int64_t *indices, int B, int hq, int wq,
                           float *out_nchw, void *ws, size_t ws_bytes);
 
+/* The network as an encoder (image -> VQ index maps, no decoder) and the code-usage histogram of index maps: declared in
+ * femasr_hip_encode.h, which is part of this interface and is included here. */
+#include "femasr_hip_encode.h"
+
 /* Per-kernel timing (HIP events recorded on `stream` around every launch) while enabled.
  * Slots = one per conv_igemm instantiation + one per small-kernel family; femasr_profile_get
  * synchronises the recorded events and returns, for launches since the last reset, the summed
