@@ -43,7 +43,7 @@ class ConvArgs(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 107      # femasr_version(): (additive, number kept: femasr_encode / femasr_encode_workspace_bytes, femasr_index_histogram / _workspace_bytes; femasr_channels_split_u8 / _merge_u8, femasr_png_filter_u8; femasr_png_filter_rgb8; femasr_dihedral_expand / _merge and their _u8 forms; femasr_repack_k1_f16, the ksz = 1 meaning of w_f16, linear_math 2) femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
+ABI_VERSION = 107      # femasr_version(): (additive, number kept: femasr_resample_u8 / femasr_resample_tile; femasr_encode / femasr_encode_workspace_bytes, femasr_index_histogram / _workspace_bytes; femasr_channels_split_u8 / _merge_u8, femasr_png_filter_u8; femasr_png_filter_rgb8; femasr_dihedral_expand / _merge and their _u8 forms; femasr_repack_k1_f16, the ksz = 1 meaning of w_f16, linear_math 2) femasr_conv_args ends with w_f16, femasr_repack_oihw_f16, decoder_math 4; 106: femasr_blend_tiles / femasr_blend_tiles_u8; 105: femasr_niqe_*, femasr_imresize*; 104: the femasr_psnr_ssim* entry points; 103: FEMASR_ACT_RELU, femasr_lpips_* 
 PRO_NONE, PRO_GN_SILU, PRO_LN = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -160,6 +160,11 @@ ENCODE_SIGNATURES = {
     'femasr_index_histogram_workspace_bytes': (c_int, [c_int, c_i64, c_int, ctypes.POINTER(szt)]),
     'femasr_index_histogram': (c_int, [vp, vp, c_int, c_i64, c_int, vp, vp, vp, szt]),
 }
+# the bicubic resample of uint8 images to an arbitrary size: include/femasr_hip_resample.h (included by femasr_hip.h; part of the interface)
+RESAMPLE_SIGNATURES = {
+    'femasr_resample_u8': (c_int, [vp, vp, c_int, c_int, c_int, vp, c_int, c_int, vp, vp, c_int, vp, vp, c_int]),
+    'femasr_resample_tile': (c_int, []),
+}
 # test / measurement hooks: include/femasr_hip_debug.h (exported by the library, not part of the drop-in interface)
 DEBUG_SIGNATURES = {
     'femasr_debug_set_wino_limits': (c_int, [vp, c_int, c_int]),
@@ -188,7 +193,7 @@ def load():
     if lib.femasr_version() != ABI_VERSION:
         raise FemasrError(f'{SO_PATH} reports ABI version {lib.femasr_version()}, this binding is written for {ABI_VERSION} '
                           '(femasr_conv_args layout): rebuild with `python femasr_amd/csrc/build.py --force`')
-    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -28,6 +28,27 @@ def load_weights(model, path):
     return model.load_state_dict(sd, strict=False)
 
 
+def _final_scale(text):
+    """--final-scale: the flag's text as an exact fraction ('3', '1.5', '1.1', '3/2')."""
+    from fractions import Fraction
+    try:
+        f = Fraction(text)
+    except (ValueError, ZeroDivisionError):
+        raise argparse.ArgumentTypeError(f'expected a number such as 3, 1.5 or 3/2, got {text!r}') from None
+    if f <= 0:
+        raise argparse.ArgumentTypeError(f'expected a positive number, got {text!r}')
+    return f
+
+
+def _final_size(text):
+    """--final-size: 'WxH' -> (W, H)."""
+    import re
+    m = re.fullmatch(r'([1-9][0-9]*)[xX]([1-9][0-9]*)', text.strip())
+    if not m:
+        raise argparse.ArgumentTypeError(f'expected WIDTHxHEIGHT in pixels such as 3840x2160, got {text!r}')
+    return int(m.group(1)), int(m.group(2))
+
+
 class _Half(argparse.Action):
     """--half: both half-precision modes at once (a later --linear-math / --decoder-math still overrides its side)."""
 
@@ -77,6 +98,14 @@ def build_parser():
     ap.add_argument('--alpha', choices=['bicubic', 'network'], default='bicubic',
                     help="with --keep-format, how the alpha channel is upscaled: 'bicubic' (MATLAB bicubic, clipped and rounded) or 'network' "
                          '(the alpha plane takes the same forward as the colour, without the colour fix)')
+    final = ap.add_mutually_exclusive_group()
+    final.add_argument('--final-scale', type=_final_scale, default=None, metavar='F',
+                       help="size of the written image as a multiple of the INPUT's size: 3, 1.5, 3/2, 1 (ceil of size times F, exact "
+                            "arithmetic).  -s/--out_scale stays the NETWORK's factor (2 or 4, the weights decide); its result is resampled "
+                            'once on the GPU, MATLAB bicubic with antialiasing, to the final size (femasr_amd.resample; each axis within '
+                            "1/8 .. 8 of the network's result).  Off by default: the network's result is written as it is")
+    final.add_argument('--final-size', type=_final_size, default=None, metavar='WxH',
+                       help='the same with an exact size in pixels for every image, e.g. 3840x2160; the aspect ratio may change')
     return ap
 
 
@@ -204,9 +233,24 @@ def _run(args, model, paths, dev, rank, world, fix, writer, fd, Image):
         return model.test_tile_u8(xu8, args.tile_size, args.tile_pad, blend=args.blend, **fix)
 
     plain = {k: v for k, v in fix.items() if k != 'color_fix'}              # the alpha plane's forward: everything but the colour fix
+    resample = None
+    if args.final_scale is not None or args.final_size is not None:
+        from femasr_amd import resample                                     # (--final-scale / --final-size: imported only with them)
     for path, img in _decoded(paths, 2 if args.io_threads >= 1 else 0, args.keep_format):
         img_name = os.path.basename(path)
         xu8 = torch.from_numpy(img).to(dev)
+        final = None                                                        # (out_h, out_w) where it is not the network's own size
+        if resample is not None:
+            h, w = img.shape[:2]
+            final = resample.target_size(h, w, args.out_scale, args.final_scale, args.final_size)
+            if final == (args.out_scale * h, args.out_scale * w):
+                final = None
+            else:
+                try:                                                        # refused before the forward runs
+                    resample.prepare(args.out_scale * h, args.out_scale * w, final[0], final[1], dev)
+                except (resample.ResampleRatio, resample.ResampleTooSmall) as e:
+                    raise SystemExit(f"{path}: the network's {args.out_scale * w}x{args.out_scale * h} result cannot be resampled to "
+                                     f'{final[1]}x{final[0]} ({e})')
         if args.keep_format:
             # the input's channels (femasr_amd.channels): split -> the same forward -> merge; an RGB image is forward(xu8) itself
             try:
@@ -216,6 +260,9 @@ def _run(args, model, paths, dev, rank, world, fix, writer, fd, Image):
                                  'pass --alpha network')
         else:
             u8 = forward(xu8, fix)
+        if final is not None and u8 is not None:
+            # once, on the final bytes of the rank that holds them: behind blend, colour fix, self-ensemble and the alpha merge
+            u8 = resample.resample_u8(u8, final[0], final[1])
         if writer is not None:
             writer.submit(u8, os.path.join(args.output, img_name))
         elif rank == 0:

@@ -596,6 +596,10 @@ int femasr_channels_merge_u8(void *stream, const uint8_t *rgb, const uint8_t *al
                              int channels, const double *w_h, const int32_t *idx_h, int taps_h, const double *w_w, const int32_t *idx_w,
                              int taps_w, uint8_t *out);
 
+/* Bicubic resample of an interleaved uint8 image (C = 1..4) to an arbitrary size, each axis at its own ratio (opt-in, femasr_amd.resample,
+ * DESIGN.md 23): declared in femasr_hip_resample.h, which is part of this interface and is included here. */
+#include "femasr_hip_resample.h"
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
