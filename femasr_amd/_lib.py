@@ -165,6 +165,12 @@ RESAMPLE_SIGNATURES = {
     'femasr_resample_u8': (c_int, [vp, vp, c_int, c_int, c_int, vp, c_int, c_int, vp, vp, c_int, vp, vp, c_int]),
     'femasr_resample_tile': (c_int, []),
 }
+# the fast JPEG output - coefficients on the GPU, Huffman coding on the host: include/femasr_hip_jpeg.h (included by femasr_hip.h; part of the interface)
+JPEG_SIGNATURES = {
+    'femasr_jpeg_coefficients_u8': (c_int, [vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp]),
+    'femasr_jpeg_entropy_rows': (ctypes.c_longlong, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, szt]),
+    'femasr_jpeg_entropy_bound': (szt, [c_int, c_int, c_int, c_int]),
+}
 # test / measurement hooks: include/femasr_hip_debug.h (exported by the library, not part of the drop-in interface)
 DEBUG_SIGNATURES = {
     'femasr_debug_set_wino_limits': (c_int, [vp, c_int, c_int]),
@@ -193,7 +199,7 @@ def load():
     if lib.femasr_version() != ABI_VERSION:
         raise FemasrError(f'{SO_PATH} reports ABI version {lib.femasr_version()}, this binding is written for {ABI_VERSION} '
                           '(femasr_conv_args layout): rebuild with `python femasr_amd/csrc/build.py --force`')
-    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

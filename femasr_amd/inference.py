@@ -91,6 +91,13 @@ def build_parser():
                          'PNG run on the GPU, N threads deflate and write behind the forward (femasr_amd.pngio: the same pixels, not the '
                          'same file bytes), one more thread decodes up to two inputs ahead')
     ap.add_argument('--png-level', type=int, default=6, metavar='0..9', help="deflate level of --io-threads N >= 1 (default 6, PIL's)")
+    ap.add_argument('--jpeg-quality', type=int, default=None, metavar='1..100',
+                    help="quality of the outputs named .jpg / .jpeg (default: unset - Image.save's own defaults, quality 75 with 4:2:0 chroma, "
+                         'as ever).  With --io-threads N >= 1 such outputs take the fast JPEG path: colour, DCT and quantisation in one '
+                         'launch on the GPU, Huffman coding in restart intervals on the N threads (femasr_amd.jpegio: a baseline JPEG of '
+                         "its own definition, not libjpeg's bytes); with --io-threads 0 they go through Image.save(quality=, subsampling=)")
+    ap.add_argument('--jpeg-subsampling', choices=['420', '444'], default=None,
+                    help='chroma subsampling of --jpeg-quality (default 420; 444 keeps full-resolution chroma); refused without --jpeg-quality')
     ap.add_argument('--keep-format', action='store_true',
                     help="the output has the input's channels: a gray image (modes L, 1) comes back gray, gray + alpha (LA) and RGBA (also a "
                          'palette image with transparency) keep their alpha channel (femasr_amd.channels; off by default: every input is '
@@ -107,6 +114,22 @@ def build_parser():
     final.add_argument('--final-size', type=_final_size, default=None, metavar='WxH',
                        help='the same with an exact size in pixels for every image, e.g. 3840x2160; the aspect ratio may change')
     return ap
+
+
+def check_jpeg_flags(args):
+    """--jpeg-quality / --jpeg-subsampling: a bad value ends the run before anything loads; args.jpeg_subsampling becomes '420' by default."""
+    if args.jpeg_quality is None:
+        if args.jpeg_subsampling is not None:
+            raise SystemExit('--jpeg-subsampling needs --jpeg-quality')
+        return
+    if not 1 <= args.jpeg_quality <= 100:
+        raise SystemExit(f'--jpeg-quality must be in 1..100, got {args.jpeg_quality}')
+    if args.jpeg_subsampling is None:
+        args.jpeg_subsampling = '420'
+
+
+def _is_jpeg_name(name):
+    return name.lower().endswith(('.jpg', '.jpeg'))
 
 
 def _decode(path, keep_format=False):
@@ -173,6 +196,7 @@ def main(argv=None):
     from femasr_amd.archs.femasr_arch import FeMaSRNet
 
     args = build_parser().parse_args(argv)
+    check_jpeg_flags(args)
 
     if not torch.cuda.is_available():
         raise SystemExit('femasr_amd.inference needs a GPU (there is no CPU fallback)')
@@ -207,7 +231,8 @@ def main(argv=None):
     writer = None
     if args.io_threads >= 1 and rank == 0:
         from femasr_amd import pngio
-        writer = pngio.PngWriter(threads=min(args.io_threads, pngio.MAX_THREADS), level=args.png_level)
+        writer = pngio.PngWriter(threads=min(args.io_threads, pngio.MAX_THREADS), level=args.png_level,
+                                 **({} if args.jpeg_quality is None else {'jpeg_quality': args.jpeg_quality, 'jpeg_subsampling': args.jpeg_subsampling}))
     try:
         _run(args, model, paths, dev, rank, world, fix, writer, fd, Image)
     finally:
@@ -266,7 +291,10 @@ def _run(args, model, paths, dev, rank, world, fix, writer, fd, Image):
         if writer is not None:
             writer.submit(u8, os.path.join(args.output, img_name))
         elif rank == 0:
-            Image.fromarray(u8.cpu().numpy(), channels.MODES[u8.shape[2] if u8.dim() == 3 else 1]).save(os.path.join(args.output, img_name))
+            # (--jpeg-quality without a writer: PIL's encoder at the same settings; its subsampling 0 is 4:4:4, 2 is 4:2:0)
+            how = ({'quality': args.jpeg_quality, 'subsampling': 0 if args.jpeg_subsampling == '444' else 2}
+                   if args.jpeg_quality is not None and _is_jpeg_name(img_name) else {})
+            Image.fromarray(u8.cpu().numpy(), channels.MODES[u8.shape[2] if u8.dim() == 3 else 1]).save(os.path.join(args.output, img_name), **how)
 
 
 if __name__ == '__main__':

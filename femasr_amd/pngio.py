@@ -7,6 +7,7 @@ written behind the forward.  Nothing here changes a pixel: the files decode to e
     encode_png(rows, width, height, level, pool)  filtered scanlines -> the bytes of a PNG file (write_png: the same into a file object)
     adler32_combine(a1, a2, len2)                 the Adler-32 of a concatenation from the Adler-32 of its parts
     PngWriter(threads=8, depth=3)                 submit(u8_cuda, path): filter + D2H on the current stream, encode + write on threads
+                                                  (jpeg_quality=Q: .jpg / .jpeg paths take the fast JPEG path of femasr_amd.jpegio)
 
 Definition.  img: uint8 (H,W,3).  raw[y] = img[y].reshape(3W); per row y and byte i, with x = raw[y][i]:
     a = raw[y][i-3] (0 if i < 3),  b = raw[y-1][i] (0 if y == 0),  c = raw[y-1][i-3] (0 if either is outside)
@@ -263,14 +264,24 @@ class PngWriter:
     an event - then it returns.  A writer thread waits for the event, deflates the bands on the shared pool of `threads` threads and writes
     the file.  At most `depth` images are in flight: submit blocks beyond that.  A path that does not end in .png (any case) gets a plain
     D2H copy and `Image.save` in the writer thread.  The first exception of a worker is re-raised by the next submit or by close().
-    No GPU stream and no process is created; thread counts are arguments (capped at 16), never derived from the machine."""
+    No GPU stream and no process is created; thread counts are arguments (capped at 16), never derived from the machine.
 
-    def __init__(self, threads=8, depth=3, level=6, stage=None):
+    jpeg_quality=Q (1..100; None, the default: nothing changes): a path that ends in .jpg or .jpeg (any case) with a 1- or 3-channel image
+    takes the fast JPEG path instead of `Image.save` - submit launches the coefficient kernel (femasr_amd.jpegio.coefficients_gpu:
+    colour, DCT, quantisation at quality Q and chroma `jpeg_subsampling`, '420' or '444') and copies the int16 planes to a pinned buffer
+    without blocking; the writer thread Huffman-codes bands of MCU rows on the shared pool and writes the file: the bytes of
+    jpegio.encode_ref.  Two- and four-channel images on such a path stay with `Image.save`, which refuses them as ever."""
+
+    def __init__(self, threads=8, depth=3, level=6, stage=None, jpeg_quality=None, jpeg_subsampling='420'):
         self.threads = clamp_threads(threads)
         self.depth = clamp_threads(depth)
         if not isinstance(level, int) or isinstance(level, bool) or not 0 <= level <= 9:
             raise ValueError(f'png level must be an integer in 0..9, got {level!r}')
         self.level = level
+        self.jpeg_quality = self.jpeg_subsampling = None
+        if jpeg_quality is not None:
+            from . import jpegio
+            self.jpeg_quality, self.jpeg_subsampling = jpegio._check_params(jpeg_quality, jpeg_subsampling)
         self._stage = stage or self._gpu_stage
         self._pinned = _PinnedPool()
         self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix='png-band')
@@ -311,6 +322,43 @@ class PngWriter:
             keep.clear()
         return host.numpy(), wait, lambda: self._pinned.give(buf)
 
+    def _gpu_jpeg_stage(self, u8):
+        """(host int16 array of every plane, plane shapes, wait(), release()): the GPU part of a submit on the fast JPEG path."""
+        import torch
+        from . import jpegio
+        flat, views = jpegio.coefficients_flat_gpu(u8, self.jpeg_quality, self.jpeg_subsampling)
+        buf = self._pinned.take(2 * flat.numel())
+        host = buf[:2 * flat.numel()].view(torch.int16)
+        host.copy_(flat, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(u8.device))
+        keep = [flat]                                         # the device buffer lives until the copy has run
+
+        def wait():
+            ev.synchronize()
+            keep.clear()
+        return host.numpy(), [tuple(v.shape) for v in views], wait, lambda: self._pinned.give(buf)
+
+    def _jpeg_job(self, path, width, height, host, shapes, wait, release):
+        try:
+            from . import jpegio
+            wait()
+            comps, off = [], 0
+            for shape in shapes:
+                n = shape[0] * shape[1] * 64
+                comps.append(host[off:off + n].reshape(shape))
+                off += n
+            data = jpegio.encode_jpeg(comps, width, height, self.jpeg_quality, self.jpeg_subsampling, self._pool)
+            with open(path, 'wb') as f:
+                f.write(data)
+        except BaseException as e:                            # kept for the caller: nothing is dropped silently
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+        finally:
+            release()
+            self._slots.release()
+
     def _raise_pending(self):
         with self._lock:
             err, self._error = self._error, None
@@ -340,16 +388,24 @@ class PngWriter:
         self._raise_pending()
         path = str(path)
         is_png = path.lower().endswith('.png')
+        is_jpeg = (self.jpeg_quality is not None and path.lower().endswith(('.jpg', '.jpeg')) and
+                   (len(u8.shape) == 2 or (len(u8.shape) == 3 and u8.shape[2] == 3)))
         self._slots.acquire()                                 # blocks while `depth` images are in flight
         try:
             height, width = int(u8.shape[0]), int(u8.shape[1])
             channels = int(u8.shape[2]) if len(u8.shape) == 3 else 1
-            host, wait, release = self._stage(u8, is_png)
+            if is_jpeg:
+                host, shapes, wait, release = self._gpu_jpeg_stage(u8)
+            else:
+                host, wait, release = self._stage(u8, is_png)
         except BaseException:
             self._slots.release()
             raise
         self._pending = [f for f in self._pending if not f.done()]
-        self._pending.append(self._writers.submit(self._job, path, is_png, width, height, channels, host, wait, release))
+        if is_jpeg:
+            self._pending.append(self._writers.submit(self._jpeg_job, path, width, height, host, shapes, wait, release))
+        else:
+            self._pending.append(self._writers.submit(self._job, path, is_png, width, height, channels, host, wait, release))
 
     def close(self):
         """Waits for every file; re-raises the first worker exception.  Idempotent."""

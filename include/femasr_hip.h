@@ -600,6 +600,10 @@ int femasr_channels_merge_u8(void *stream, const uint8_t *rgb, const uint8_t *al
  * DESIGN.md 23): declared in femasr_hip_resample.h, which is part of this interface and is included here. */
 #include "femasr_hip_resample.h"
 
+/* Fast JPEG output (opt-in, femasr_amd.jpegio): colour, DCT and quantisation of a uint8 image in one launch, and the host-side
+ * Huffman coder of its restart intervals: declared in femasr_hip_jpeg.h, which is part of this interface and is included here. */
+#include "femasr_hip_jpeg.h"
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
