@@ -171,6 +171,16 @@ JPEG_SIGNATURES = {
     'femasr_jpeg_entropy_rows': (ctypes.c_longlong, [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, szt]),
     'femasr_jpeg_entropy_bound': (szt, [c_int, c_int, c_int, c_int]),
 }
+# synthesis of low-quality inputs - blur, resample, noise, quantisation, JPEG decode: include/femasr_hip_degrade.h (included by femasr_hip.h; part of the interface)
+c_u64 = ctypes.c_uint64
+DEGRADE_SIGNATURES = {
+    'femasr_degrade_blur_f32': (c_int, [vp, vp, c_int, c_int, vp, c_int, c_int, vp]),
+    'femasr_degrade_resize_f32': (c_int, [vp, vp, c_int, c_int, vp, c_int, c_int, vp, vp, c_int, vp, vp, c_int, vp, vp]),
+    'femasr_degrade_noise_f32': (c_int, [vp, vp, vp, ctypes.c_longlong, c_u64, c_int, ctypes.POINTER(ctypes.c_double), c_u64]),
+    'femasr_degrade_quantize_u8': (c_int, [vp, vp, vp, ctypes.c_longlong]),
+    'femasr_degrade_unit_f32': (c_int, [vp, vp, c_int, c_int, c_int, vp]),
+    'femasr_jpeg_decode_u8': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, c_int]),
+}
 # test / measurement hooks: include/femasr_hip_debug.h (exported by the library, not part of the drop-in interface)
 DEBUG_SIGNATURES = {
     'femasr_debug_set_wino_limits': (c_int, [vp, c_int, c_int]),
@@ -199,7 +209,7 @@ def load():
     if lib.femasr_version() != ABI_VERSION:
         raise FemasrError(f'{SO_PATH} reports ABI version {lib.femasr_version()}, this binding is written for {ABI_VERSION} '
                           '(femasr_conv_args layout): rebuild with `python femasr_amd/csrc/build.py --force`')
-    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

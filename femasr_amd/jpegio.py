@@ -8,6 +8,9 @@ launch on the GPU, the entropy coding in independent restart intervals on the wr
     encode_jpeg(coeffs, width, height, quality, subsampling, pool=None)
                                                     the same bytes with femasr_jpeg_entropy_rows coding bands of MCU rows on `pool`
     quant_tables(quality) / quant_multipliers(q)    the two scaled tables; the reciprocal multipliers the kernel divides with
+    decode_ref(components, quality, subsampling, H, W)   the DEFINITION of the way back (numpy, integers only): uint8 (H,W) / (H,W,3) pixels
+    decode_gpu(planes, quality, subsampling, H, W, float32=False)
+                                                    the same pixels from ONE femasr_jpeg_decode_u8 launch (csrc/degrade.hip)
 
 Definition.  img: uint8 (H,W) gray or (H,W,3) RGB, 1 <= H, W <= 65535.  quality: an integer 1..100.  subsampling: '444' or '420' (a gray image
 ignores it).  All arithmetic is integer (int32 suffices everywhere; numpy runs the sums in int64), `>>` is the arithmetic shift (floor).
@@ -33,6 +36,22 @@ The DCT's distance from the exact one (DCT_BOUND, before quantisation).  dT = |T
   With the table's own numbers this is dct_bound() = 0.918; what noise, checkerboards and steps show is 0.61 (tests/test_jpeg_io_host.py
   holds the derived figure, profiles/jpeg_io_report.txt has the measured ones).  A flat block of value p gives F[0][0] = 8 (p - 128) exactly and
   0 elsewhere: the rows of T for u > 0 sum to 0, and 23168^2 / 2^26 = 7.9983, off 8 by 0.0017 * 128 + 0.18 < 1/2.
+
+The way back (decode_ref; the JPEG "noise" of femasr_amd.degrade is coefficients followed by this - Huffman coding is lossless, so no entropy
+coder runs).  components: the int16 planes above, one (gray) or three.  Integers only, int32 suffices:
+  Dequantisation: F[w][u] = clip(k Q, -2047, 2047).  What the encoder above writes satisfies |k Q| <= |F| + Q / 2 <= 1025 + 127, so the clip
+      changes nothing there; it bounds the sums for planes from elsewhere.
+  Column pass  C[y][u] = (sum_w T[w][y] F[w][u] + 512) >> 10        max_y sum_w |T[w][y]| = 21641: |sum| <= 21641 * 2047 < 2^26, |C| <= 43261
+  Row pass     p[y][x] = clip(((sum_u T[u][x] C[y][u] + 32768) >> 16) + 128, 0, 255)        |sum| <= 21641 * 43261 < 2^30
+      (the transposed passes of the encoder with its shifts: C is 8 times the exact column transform, p the exact inverse within the rounding)
+  '420' chroma at pixel (y, x), c the decoded (padded) chroma plane: i = y >> 1, i' = i - 1 for even y and i + 1 for odd y, clamped to the
+      plane (replicated edge), j, j' likewise from x:  (9 c[i][j] + 3 c[i'][j] + 3 c[i][j'] + c[i'][j'] + 8) >> 4   (the triangle filter)
+  Colour (JFIF inverse, 16-bit fixed point; cb = Cb - 128, cr = Cr - 128; a gray image is its Y):
+      R = clip(Y + ((91881 cr + 32768) >> 16), 0, 255)          |91881 * 128| < 2^24
+      G = clip(Y + ((-22554 cb - 46802 cr + 32768) >> 16), 0, 255)
+      B = clip(Y + ((116130 cb + 32768) >> 16), 0, 255)
+  The planes are cropped to H x W.  Not libjpeg's decoder bit for bit (another IDCT, and libjpeg rounds the two passes of its upsampling
+  separately): tests/test_degrade_host.py holds the distance from Pillow on the bytes of encode_ref, profiles/degrade_report.txt records it.
 
 The scan (entropy_ref; femasr_jpeg_entropy_rows gives the same bytes).  Baseline Huffman with the four Annex K tables (DC / AC, luminance for
 component 0, chrominance for 1 and 2).  ONE RESTART INTERVAL PER MCU ROW (DRI = MCUs per row): the DC predictors are 0 at the start of every
@@ -185,6 +204,53 @@ def coefficients_ref(img, quality, subsampling='420'):
     quality, subsampling = _check_params(quality, subsampling)
     qy, qc = quant_tables(quality)
     return [quantise_ref(fdct_ref(p), qy if i == 0 else qc) for i, p in enumerate(planes_ref(img, subsampling))]
+
+
+# ---- the way back ----
+
+def idct_ref(f):
+    """int64 (.., 8, 8) F[w][u] -> int64 (.., 8, 8) pixels p[y][x], 0..255 (module docstring)."""
+    c = (np.einsum('wy,...wu->...yu', DCT_TABLE, f) + 512) >> 10
+    return np.clip(((np.einsum('ux,...yu->...yx', DCT_TABLE, c) + 32768) >> 16) + 128, 0, 255)
+
+
+def _plane_ref(comp, q):
+    """int16 (Hb, Wb, 64) zigzag coefficients and a natural-order table -> int64 (8 Hb, 8 Wb) plane."""
+    hb, wb = comp.shape[:2]
+    nat = np.zeros((hb, wb, 64), np.int64)
+    nat[..., ZIGZAG] = comp.astype(np.int64)
+    f = np.clip(nat * q, -2047, 2047).reshape(hb, wb, 8, 8)
+    return idct_ref(f).transpose(0, 2, 1, 3).reshape(8 * hb, 8 * wb)
+
+
+def _upsample_ref(c, height, width):
+    """The triangle filter of the module docstring: the (h, w) chroma plane at the pixels of a height x width image."""
+    y, x = np.arange(height), np.arange(width)
+    i, j = y >> 1, x >> 1
+    i2 = np.clip(i + np.where(y & 1, 1, -1), 0, c.shape[0] - 1)
+    j2 = np.clip(j + np.where(x & 1, 1, -1), 0, c.shape[1] - 1)
+    return (9 * c[i][:, j] + 3 * c[i2][:, j] + 3 * c[i][:, j2] + c[i2][:, j2] + 8) >> 4
+
+
+def decode_ref(components, quality, subsampling, height, width):
+    """The definition (module docstring): [int16 (Hb, Wb, 64)] planes of a height x width image -> uint8 (H,W) gray or (H,W,3) RGB."""
+    quality, subsampling = _check_params(quality, subsampling)
+    comps = _layout(components, subsampling)[0]
+    channels = len(comps)
+    check_shape((height, width) if channels == 1 else (height, width, 3), 'decode_ref')
+    if [c.shape[:2] for c in comps] != geometry(height, width, channels, subsampling)[2]:
+        raise ValueError(f'decode_ref: planes {[c.shape for c in comps]} are not those of a {width} x {height} image')
+    qy, qc = quant_tables(quality)
+    planes = [_plane_ref(c, qy if i == 0 else qc) for i, c in enumerate(comps)]
+    yy = planes[0][:height, :width]
+    if channels == 1:
+        return yy.astype(np.uint8)
+    if subsampling == '420':
+        cb, cr = (_upsample_ref(p, height, width) - 128 for p in planes[1:])
+    else:
+        cb, cr = (p[:height, :width] - 128 for p in planes[1:])
+    rgb = np.stack([yy + ((91881 * cr + 32768) >> 16), yy + ((-22554 * cb - 46802 * cr + 32768) >> 16), yy + ((116130 * cb + 32768) >> 16)], axis=2)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
 
 
 # ---- the scan ----
@@ -398,3 +464,27 @@ def coefficients_flat_gpu(u8, quality, subsampling='420'):
 def coefficients_gpu(u8, quality, subsampling='420'):
     """`coefficients_ref` of a uint8 (H,W) or (H,W,3) GPU tensor: [int16 (Hb, Wb, 64) GPU tensors], ONE launch on the current stream."""
     return coefficients_flat_gpu(u8, quality, subsampling)[1]
+
+
+def decode_gpu(planes, quality, subsampling, height, width, float32=False):
+    """`decode_ref` of int16 (Hb, Wb, 64) GPU planes (16-byte aligned, as coefficients_gpu returns them): a uint8 (H,W) / (H,W,3) GPU tensor,
+    or with float32=True the float32 tensor u8 / 255; ONE launch on the current stream."""
+    import torch
+    from . import _lib
+    quality, subsampling = _check_params(quality, subsampling)
+    planes = list(planes)
+    if len(planes) not in (1, 3) or any(not torch.is_tensor(p) or not p.is_cuda or p.dtype != torch.int16 or not p.is_contiguous() for p in planes):
+        raise ValueError('decode_gpu: expected one or three contiguous int16 (Hb, Wb, 64) GPU tensors')
+    channels = len(planes)
+    check_shape((height, width) if channels == 1 else (height, width, 3), 'decode_gpu')
+    if [tuple(p.shape) for p in planes] != [s + (64,) for s in geometry(height, width, channels, subsampling)[2]]:
+        raise ValueError(f'decode_gpu: planes {[tuple(p.shape) for p in planes]} are not those of a {width} x {height} image')
+    dev = planes[0].device
+    tab = device_tables(quality, dev)
+    out = torch.empty((height, width) if channels == 1 else (height, width, 3), dtype=torch.float32 if float32 else torch.uint8, device=dev)
+    p = [_lib.ptr(v) for v in planes] + [None] * (3 - channels)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().femasr_jpeg_decode_u8(torch.cuda.current_stream(dev).cuda_stream, p[0], p[1], p[2], channels,
+                                                     0 if channels == 1 else int(subsampling), height, width, _lib.ptr(tab[0]),
+                                                     None if channels == 1 else _lib.ptr(tab[1]), _lib.ptr(out), 1 if float32 else 0))
+    return out
