@@ -653,8 +653,9 @@ class FeMaSRNet(nn.Module):
         tiles of one shape class run as batched `test()` calls, and with world_size > 1 each rank
         computes a contiguous share of every class; `gather(results, classes, batch, channel, scale) -> list per rank`
         supplies the collective (femasr_amd.distributed.TileExchange: ONE RCCL all-gather on persistent buffers the tiles were
-        written into).  paste=False (ranks other than the one that needs the image): take part in the collective, skip the
-        canvas (returns None).
+        written into).  A gather that is passed is used at world_size == 1 too (one rank of a real collective); world_size > 1
+        without one is a ValueError.  paste=False (ranks other than the one that needs the image): take part in the collective,
+        skip the canvas (returns None).
         blend=True (NOT the reference's arithmetic, hence off by default): instead of discarding the halos, every canvas pixel is the
         weighted mean of the upscaled windows that contain it (linear ramps across the overlaps: tiling.blend_weight_1d)
         - no seams where neighbouring bodies meet.  The tiles, their batching and the collective are the same; only the last step
@@ -706,7 +707,8 @@ class FeMaSRNet(nn.Module):
             ev[0].record()
         # One result buffer per shape class, written in place by the batched calls (`out=`).  With a gather object that owns
         # persistent send buffers (femasr_amd.distributed.TileExchange.send_views) the buffers ARE this rank's all-gather send slab.
-        alloc = getattr(gather, 'send_views', None) if world_size > 1 else None
+        # A gather that is passed is used, in a world of one as well (one rank of a real collective: the same slab, gather and paste).
+        alloc = getattr(gather, 'send_views', None) if gather is not None else None
         if alloc is not None:
             results = alloc(classes, batch, channel, s, fmt.dtype, x.device)
         else:
@@ -727,9 +729,9 @@ class FeMaSRNet(nn.Module):
                     dst.copy_(y)
         if ev:
             ev[1].record()
-        if world_size > 1:
-            if gather is None:
-                raise ValueError('world_size > 1 needs a gather callable')
+        if world_size > 1 and gather is None:
+            raise ValueError('world_size > 1 needs a gather callable')
+        if gather is not None:
             per_rank = gather(results, classes, batch, channel, s)
         else:
             per_rank = [results]

@@ -18,8 +18,11 @@ tile's compute time, so it is issued once, un-bucketed, as
 receive - the per-rank results are views into the receive buffer.  A rank that
 does not need the image (`paste=False`) joins the collective and skips the canvas.
 
-Not measured: no node with more than one GPU was available to this build; the
-scaling curve is the driver's to record (bench.py --gpus N).
+Tested on a device: the slab path on ONE GPU with real forwards - every rank of worlds of 1, 2, 3 and 8 played in turn
+through a loopback in place of `torch.distributed` (tests/test_gpu_tile_exchange.py) -, and one rank of real RCCL in a child
+process (tests/test_gpu_rccl_one_rank.py: TileExchange and the StepGather loop).  Not covered and not measured: more than
+one device, xGMI, the scaling curve - no node with more than one GPU was available to this build; the curve is the driver's
+to record (bench.py --gpus N).
 """
 import functools
 import os

@@ -1,5 +1,10 @@
 """RCCL sanity on one GPU box: run under torchrun (any world size); checks that the tile-parallel path (one all_gather
-over the NCCL/RCCL backend) reproduces the single-process test_tile output bit for bit."""
+over the NCCL/RCCL backend) reproduces the single-process test_tile output bit for bit.
+
+Without torchrun (world size 1) a one-rank group is made and the call is `test_tile(..., world_size=1, gather=TileExchange())`:
+`test_tile_parallel` returns the plain `test_tile` in a world of one, which would compare the call with itself; `_tiled` honours a
+gather object it is given, so this leg writes the tiles into the send slab, runs the RCCL all-gather and pastes out of the receive
+buffer (tests/test_gpu_rccl_one_rank.py does the same in the suite)."""
 import os
 import sys
 
@@ -24,7 +29,10 @@ def main():
     net = net.to(dev).eval()
     x = torch.from_numpy(synth.synth_input(7, (1, 3, 200, 168))).to(dev)
     ref = net.test_tile(x, 96, 16)
-    got = fd.test_tile_parallel(net, x, 96, 16)
+    if world == 1:
+        got = net.test_tile(x, 96, 16, rank=0, world_size=1, gather=fd.TileExchange())
+    else:
+        got = fd.test_tile_parallel(net, x, 96, 16)
     same = bool(torch.equal(ref, got))
     print(f'rank {rank}/{world}: tile-parallel == test_tile: {same}; backend {torch.distributed.get_backend()}', flush=True)
     torch.distributed.barrier()
