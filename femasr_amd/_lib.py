@@ -181,6 +181,20 @@ DEGRADE_SIGNATURES = {
     'femasr_degrade_unit_f32': (c_int, [vp, vp, c_int, c_int, c_int, vp]),
     'femasr_jpeg_decode_u8': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, c_int]),
 }
+# DISTS - handle, forward, the backbone's stage maps, the L2-pool and moments units: include/femasr_hip_dists.h (included by femasr_hip.h; part of the interface)
+DISTS_SIGNATURES = {
+    'femasr_dists_create': (c_int, [c_int, ctypes.POINTER(vp)]),
+    'femasr_dists_destroy': (None, [vp]),
+    'femasr_dists_set_weight': (c_int, [vp, ctypes.c_char_p, vp, ctypes.POINTER(c_i64), c_int]),
+    'femasr_dists_finalize_weights': (c_int, [vp]),
+    'femasr_dists_workspace_bytes': (c_int, [vp, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_dists_forward': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, vp, szt, vp, vp]),
+    'femasr_dists_features': (c_int, [vp, vp, vp, vp, c_int, c_int, c_int, vp, szt, vp]),
+    'femasr_dists_l2pool': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp]),
+    'femasr_dists_moments_workspace_bytes': (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(szt)]),
+    'femasr_dists_moments': (c_int, [vp, vp, c_int, c_int, c_int, c_int, vp, szt, vp]),
+    'femasr_dists_moments_input': (c_int, [vp, vp, vp, c_int, c_int, c_int, vp, szt, vp]),
+}
 # test / measurement hooks: include/femasr_hip_debug.h (exported by the library, not part of the drop-in interface)
 DEBUG_SIGNATURES = {
     'femasr_debug_set_wino_limits': (c_int, [vp, c_int, c_int]),
@@ -209,7 +223,7 @@ def load():
     if lib.femasr_version() != ABI_VERSION:
         raise FemasrError(f'{SO_PATH} reports ABI version {lib.femasr_version()}, this binding is written for {ABI_VERSION} '
                           '(femasr_conv_args layout): rebuild with `python femasr_amd/csrc/build.py --force`')
-    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(ENCODE_SIGNATURES.items()) + list(RESAMPLE_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(DEGRADE_SIGNATURES.items()) + list(DISTS_SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

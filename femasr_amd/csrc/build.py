@@ -10,8 +10,8 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ['kernels_conv.hip', 'kernels_gemm.hip', 'kernels_gemm_bf16.hip', 'kernels_gemm_f16.hip', 'kernels_vq.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_layout.hip', 'kernels_probe.hip', 'conv_forms.hip', 'kernels_wino.hip', 'kernels_wino_up2.hip', 'kernels_conv_bf16.hip', 'kernels_conv_f16.hip', 'model.hip', 'lpips.hip', 'psnr_ssim.hip', 'niqe.hip', 'colorfix.hip', 'ensemble.hip', 'png_filter.hip', 'channels.hip', 'codebook_stats.hip', 'resample.hip', 'jpeg_dct.hip', 'degrade.hip']
-HEADERS = ['common.h', 'conv_common.h', 'halo_mma.h', 'wino_common.h', 'gemm_common.h', 'detmath.h', 'pixel.h', '../../include/femasr_hip.h', '../../include/femasr_hip_encode.h', '../../include/femasr_hip_resample.h', '../../include/femasr_hip_jpeg.h', '../../include/femasr_hip_degrade.h','../../include/femasr_hip_debug.h']
+SOURCES = ['kernels_conv.hip', 'kernels_gemm.hip', 'kernels_gemm_bf16.hip', 'kernels_gemm_f16.hip', 'kernels_vq.hip', 'kernels_norm.hip', 'kernels_attn.hip', 'kernels_layout.hip', 'kernels_probe.hip', 'conv_forms.hip', 'kernels_wino.hip', 'kernels_wino_up2.hip', 'kernels_conv_bf16.hip', 'kernels_conv_f16.hip', 'model.hip', 'lpips.hip', 'psnr_ssim.hip', 'niqe.hip', 'colorfix.hip', 'ensemble.hip', 'png_filter.hip', 'channels.hip', 'codebook_stats.hip', 'resample.hip', 'jpeg_dct.hip', 'degrade.hip', 'dists.hip']
+HEADERS = ['common.h', 'conv_common.h', 'halo_mma.h', 'wino_common.h', 'gemm_common.h', 'detmath.h', 'pixel.h', '../../include/femasr_hip.h', '../../include/femasr_hip_encode.h', '../../include/femasr_hip_resample.h', '../../include/femasr_hip_jpeg.h', '../../include/femasr_hip_degrade.h', '../../include/femasr_hip_dists.h', '../../include/femasr_hip_debug.h']
 SO = os.path.join(HERE, 'libfemasr_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
          '-fhip-fp32-correctly-rounded-divide-sqrt', '-Wno-unused-result']

@@ -21,7 +21,8 @@ uint8 SR and GT images already on the device, within 1e-9 dB / 1e-12 of these fu
 image never leaving the device.  'niqe' is the no-reference NIQE (BasicSR's calculate_niqe, restated below as calculate_niqe with its
 pieces: _niqe_y, _convolve_nearest, imresize / imresize_tables, aggd_tables, niqe_features, niqe_score_from_features) when its options
 carry `pretrained_model_path` (a local niqe_pris_params.npz): scored on sr_u8 on the GPU (femasr_amd.niqe, csrc/niqe.hip) for every image,
-also of a dataset without ground truth; only its tail (36 numbers per block) runs on the host, in the definition's own function.  Without
+also of a dataset without ground truth; only its tail (36 numbers per block) runs on the host, in the definition's own function.  'dists'
+is DISTS on the GPU (femasr_amd.dists, csrc/dists.hip) under the same keywords and on the same tensors as the LPIPS types.  Without
 a weight / parameter file (none is ever downloaded) these types, like every other type (musiq, ...), are reported as skipped (None).
 There is no CPU path: the module needs a GPU and the HIP library.
 """
@@ -33,6 +34,7 @@ from copy import deepcopy
 import numpy as np
 import torch
 
+from .. import dists as dists_metric
 from .. import imgproc
 from .. import lpips as lpips_metric
 from .. import niqe as niqe_metric
@@ -383,7 +385,8 @@ class FeMaSRModel:
         metrics = val_opt.get('metrics') or {}
         self.metric_results = {name: 0.0 for name in metrics}
         gpu_metrics = {name: self._gpu_metric(name, m) for name, m in metrics.items()
-                       if m.get('type') in lpips_metric.METRIC_NETS and m.get('pretrained_model_path')}
+                       if (m.get('type') in lpips_metric.METRIC_NETS or m.get('type') in dists_metric.METRIC_TYPES)
+                       and m.get('pretrained_model_path')}
         # psnr / ssim on the device; the CPU functions in _METRICS are their definition
         pixel_metrics = {name: psnr_ssim.create_metric(m['type'], **{k: v for k, v in m.items() if k not in ('type', 'better')})
                          for name, m in metrics.items() if m.get('type') in _METRICS}
@@ -393,7 +396,8 @@ class FeMaSRModel:
         skipped = sorted(name for name, m in metrics.items()
                          if m.get('type') not in _METRICS and name not in gpu_metrics and name not in noref_metrics)
         if skipped:
-            logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), niqe needs '
+            logger.warning('metrics %s are skipped: lpips / lpips-vgg need `pretrained_model_path` (a local LPIPS weight file), dists needs '
+                           '`pretrained_model_path` (a local DISTS weight file), niqe needs '
                            '`pretrained_model_path` (a local niqe_pris_params.npz), other pyiqa types are not implemented in this build',
                            skipped)
         # `val: io_threads: N` (extension key; absent: Image.save here, as ever): the saves go through a pngio.PngWriter - PNG row filters
@@ -456,11 +460,12 @@ class FeMaSRModel:
         return n
 
     def _gpu_metric(self, name, m):
-        """The LPIPS module of metric `name` (built once per model and option set)."""
+        """The LPIPS or DISTS module of metric `name` (built once per model and option set)."""
         cache = self.__dict__.setdefault('_lpips_metrics', {})
         key = (name, m.get('type'), m.get('pretrained_model_path'), m.get('backbone_model_path'))
         if key not in cache:
-            cache[key] = lpips_metric.create_metric(m['type'], device=self.device, pretrained_model_path=m['pretrained_model_path'],
+            factory = dists_metric if m['type'] in dists_metric.METRIC_TYPES else lpips_metric
+            cache[key] = factory.create_metric(m['type'], device=self.device, pretrained_model_path=m['pretrained_model_path'],
                                                     backbone_model_path=m.get('backbone_model_path'))
         return cache[key]
 

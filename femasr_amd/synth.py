@@ -146,3 +146,22 @@ def lpips_state(shapes, seed: int = 0):
             lim = float(np.sqrt(6.0 / (shape[1] * shape[2] * shape[3])))
             out[key] = uniform(seed, key, shape, -lim, lim)
     return out
+
+
+def dists_state(seed: int = 0, shapes=None):
+    """Synthetic DISTS weights for {canonical key: shape} (default: femasr_amd.dists.expected_shapes()): convs N(0, 2 / (9 Cin)), biases
+    0.05 N(0, 1), alpha and beta |0.1 + 0.01 N(0, 1)| (positive, as the trained vectors are).  With these the stage outputs stay O(1)
+    through all five stages.  Drawn from numpy's PCG64 keyed by (seed, key)."""
+    if shapes is None:
+        from .dists import expected_shapes
+        shapes = expected_shapes()
+    out = {}
+    for key, shape in shapes.items():
+        n = np.random.default_rng([int(seed), _fnv1a64(key) & 0xFFFFFFFF]).standard_normal(tuple(shape))
+        if key in ('alpha', 'beta'):
+            out[key] = np.abs(0.1 + 0.01 * n).astype(np.float32)
+        elif key.endswith('.bias'):
+            out[key] = (0.05 * n).astype(np.float32)
+        else:
+            out[key] = (n * np.sqrt(2.0 / (9.0 * shape[1]))).astype(np.float32)
+    return out

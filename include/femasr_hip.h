@@ -608,6 +608,10 @@ int femasr_channels_merge_u8(void *stream, const uint8_t *rgb, const uint8_t *al
  * the decoder of the JPEG coefficient planes: declared in femasr_hip_degrade.h, which is part of this interface and is included here. */
 #include "femasr_hip_degrade.h"
 
+/* DISTS, the full-reference metric reported beside LPIPS (femasr_amd.dists): handle, forward and the pool / moments units:
+ * declared in femasr_hip_dists.h, which is part of this interface and is included here. */
+#include "femasr_hip_dists.h"
+
 /* ---- measurement support ---- */
 /* Sustained-clock probe: FEMASR_CLOCK_PROBE_BLOCKS blocks of 4 waves stream `mfmas_per_wave` back-to-back fp32 MFMAs (the load
  * of the hot kernels; 64 shader cycles each) and write the s_memtime ticks of their loop to ticks[blocks*4].  ticks / wall time
